@@ -49,6 +49,11 @@ DEFER_TUPLES = 8_000_000_000  # k-mer occurrences buffered per flush of the part
 PLACE_BINS = 16  # mcx_graph_configure("place_bins"): each half of the sub-table bins is the best of up to this many allocations by the
                 # split's write-pattern probe (where 8 GB of bins lie in HBM decides 13 % of the split: profiles/r06_experiments.md)
 HEADLINE_DEFER = DEFER_TUPLES  # what `value` was measured with (main() sets it: the whole timed region in one flush)
+MAX_RESIDENT_STEPS = 40  # distinct 5M-read batches in HBM (30 GB): step i of a longer run builds batch i mod 40 (more distinct
+                         # reads than that would fill the 2^30-slot table: C4 (k = 63) adds 20 M k-mers per step to 200 M)
+DUMP_BYTES = 64 << 20    # --dump-outputs: bytes of all the .npy files together at most
+DUMP_SAMPLE_SHIFT = 9    # --dump-outputs: the graph's records whose mixed key falls in the lowest 1/2^9 of the range
+DUMP_SEED = 0x9E3779B97F4A7C15
 # algorithmic bytes per k-mer occurrence of every kernel of that path
 KERNEL_ALG_BYTES = {"k_stream": 21.25, "k_stream_bin": 1.25 + 8.0, "k_tuples_bin": 16.0, "k_lds_insert": 8.0,
                     "k_insert_tuples": 29.0, "k_stream_superk": 1.25 + 2.3, "k_superk_bin": 2.3 + 8.0}
@@ -1062,6 +1067,72 @@ def sharded_main(mcx, shard, dist, args, device, local_rank, rank, world, force_
     return out
 
 
+def _mix64(x):
+    """splitmix64 finaliser over a uint64 array (wrapping arithmetic)"""
+    x = x ^ (x >> np.uint64(30))
+    x = x * np.uint64(0xBF58476D1CE4E5B9)
+    x = x ^ (x >> np.uint64(27))
+    x = x * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def dump_outputs(graph, outdir):
+    """--dump-outputs: what the timed build hands its caller -- the graph's records (k-mer key words, per-colour
+    coverage, per-colour edge bits) -- as .npy files in float64 / float32, under DUMP_BYTES in all.  The records are
+    a fixed sample: those whose seeded hash of the key lies in the lowest 2^-DUMP_SAMPLE_SHIFT of the range (capped
+    at the smallest hashes that fit), sorted by key, so that it does not depend on where the table placed them.
+    Next to them, whole-graph figures: the k-mer count, the order-independent checksum, the load statistics and the
+    k-mer coverage histogram."""
+    import ctypes as C
+    from mccortex_amd.graph import SINK_FN
+    os.makedirs(outdir, exist_ok=True)
+    W, ncols = graph.W, graph.ncols
+    rs = 8 * W + 5 * ncols
+    limit = np.uint64(((1 << 64) - 1) >> DUMP_SAMPLE_SHIFT)
+    parts = []
+
+    def sink(_ctx, ptr, n):
+        rec = np.frombuffer((C.c_uint8 * n).from_address(ptr), dtype=np.uint8).reshape(-1, rs)
+        keys = rec[:, :8 * W].copy().view(np.uint64).reshape(-1, W)
+        h = np.full(len(keys), DUMP_SEED, dtype=np.uint64)
+        for w in range(W):
+            h = _mix64(h ^ keys[:, w])
+        sel = np.nonzero(h <= limit)[0]
+        parts.append((h[sel], rec[sel].copy()))
+        return 0
+
+    cb = SINK_FN(sink)
+    rc = graph.L.mcx_graph_export(graph.h, 0, cb, None)
+    if rc != 0:
+        raise RuntimeError("dump_outputs: mcx_graph_export failed (%d)" % rc)
+    h = np.concatenate([p_[0] for p_ in parts]) if parts else np.zeros(0, np.uint64)
+    rec = np.concatenate([p_[1] for p_ in parts]) if parts else np.zeros((0, rs), np.uint8)
+    nbins = 1024
+    row_bytes = 2 * W * 8 + ncols * 8 + ncols * 4
+    cap = (DUMP_BYTES - 64 * 1024 - nbins * 8) // row_bytes
+    if len(h) > cap:
+        rec = rec[np.argsort(h, kind="stable")[:cap]]
+    keys = rec[:, :8 * W].copy().view(np.uint64).reshape(-1, W)
+    rec = rec[np.lexsort([keys[:, w] for w in reversed(range(W))])] if len(rec) else rec
+    keys = rec[:, :8 * W].copy().view(np.uint64).reshape(-1, W)
+    covg = rec[:, 8 * W:8 * W + 4 * ncols].copy().view(np.uint32).reshape(-1, ncols)
+    edges = rec[:, 8 * W + 4 * ncols:]
+    # every 64-bit key word as its two 32-bit halves (high first): exact in float64
+    halves = np.empty((len(keys), 2 * W), dtype=np.float64)
+    halves[:, 0::2] = (keys >> np.uint64(32)).astype(np.float64)
+    halves[:, 1::2] = (keys & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    cs, nodes = graph.checksum()
+    st = graph.device_stats()
+    stats = [nodes, cs >> 32, cs & 0xFFFFFFFF] + [getattr(st, f) for f, _ in st._fields_]
+    arrays = {"sample_kmer_keys": halves, "sample_kmer_covg": covg.astype(np.float64), "sample_kmer_edges": edges.astype(np.float32),
+              "graph_stats": np.array(stats, dtype=np.float64), "covg_histogram": graph.covg_histogram(nbins).astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {"dir": outdir, "files": sorted(n + ".npy" for n in arrays), "sampled_kmers": int(len(keys)), "graph_kmers": int(nodes),
+            "what": "graph_stats = [k-mers, checksum high 32 bits, checksum low 32 bits, then mcx_load_stats in field order]; "
+                    "sample_kmer_keys = key words as (high, low) 32-bit halves; the sample is sorted by key"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1087,10 +1158,15 @@ def main():
     ap.add_argument("--defer-tuples", type=int, default=0,
                     help="k-mer occurrences buffered per flush; default: the whole timed region in ONE flush (one pass over the "
                          "table) when that fits 16 G occurrences = 136 GB of the part's 288 GB, never below %d" % DEFER_TUPLES)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they built (a fixed sample of the graph's records and whole-graph "
+                         "figures) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--inprocess-multi", type=int, default=0,
                     help="(used by the N > 1 run itself, as a subprocess) the C ABI's one-process table over devices 0..N-1 "
                          "(mcx_graph_create_multi: what `mccortex31 build -D 0,1,..` runs) on the same reads; prints its own JSON line")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.inprocess_multi or os.environ.get("MCX_BENCH_FORCE_SHARD") == "1"):
+        raise SystemExit("bench.py: --dump-outputs is implemented for the one-GPU run only")
     if not args.defer_tuples:
         # One flush for the timed region: every flush streams the 16 GiB table through LDS once, and the part has the HBM
         # for it (bins 8.5 B per buffered occurrence).  A launch is booked with one occurrence per START POSITION of its
@@ -1161,11 +1237,13 @@ def main():
 
     B = args.batch_reads
     nsteps, nwarm = args.steps, args.warmup
+    # distinct timed batches in HBM; the warm-up batches follow them
+    nres = min(nsteps, MAX_RESIDENT_STEPS)
     if args.iid:
-        batches = [make_batch_iid(B, seed=1000 + i, device=device) for i in range(nsteps + nwarm)]
+        batches = [make_batch_iid(B, seed=1000 + i, device=device) for i in range(nres + nwarm)]
     else:
         genome = make_genome(args.genome, device, seed=42)
-        batches = [make_batch(genome, B, seed=1000 + i, device=device, err_rate=args.err) for i in range(nsteps + nwarm)]
+        batches = [make_batch(genome, B, seed=1000 + i, device=device, err_rate=args.err) for i in range(nres + nwarm)]
         del genome
     torch.cuda.synchronize()
     torch.cuda.empty_cache()  # hand the generator's temporaries back before the graph allocates
@@ -1199,7 +1277,8 @@ def main():
         torch.cuda.synchronize()
         graph.sync()
 
-    run_steps(range(nsteps, nsteps + nwarm))
+    timed = [i % nres for i in range(nsteps)]   # (step i builds batch i; past MAX_RESIDENT_STEPS, batch i mod that)
+    run_steps(range(nres, nres + nwarm))
     fence()
     graph.reset()
     fence()
@@ -1208,7 +1287,7 @@ def main():
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     ev0.record(ext)
-    run_steps(range(nsteps))
+    run_steps(timed)
     fence()
     ev1.record(ext)
     dt = time.perf_counter() - t0
@@ -1219,6 +1298,7 @@ def main():
     kmers_local = st.num_kmers_loaded  # k-mer occurrences this rank k-merised (== inserted job-wide)
     prof = graph.profile()  # {kernel: (launches, total ms)} of the timed region, measured live with HIP events
     cs_local, nodes_local = graph.checksum()   # order-independent checksum of this rank's k-mers
+    dumped = dump_outputs(graph, args.dump_outputs) if args.dump_outputs else None
     # Per-kernel durations that mean something: with the flush overlap on (the default, and what `value` is
     # measured with) the insert of one region group runs beside the split of the next, and the HIP-event spans
     # of the two kernels contain each other.  A second pass over the same steps with the overlap off gives
@@ -1231,7 +1311,7 @@ def main():
         graph.configure("profile", 1)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(ext)
-        run_steps(range(nsteps))
+        run_steps(timed)
         fence()
         e1.record(ext)
         torch.cuda.synchronize()
@@ -1267,6 +1347,8 @@ def main():
                        "distinct_kmers_total": nodes_total, "graph_checksum": "%016x" % cs_total,
                        "table_passes_rank0": ist["flushes"], "fallback_inserts_rank0": ist["fallback_inserts"], "foreign_inserts_rank0": ist["foreign_inserts"]},
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         # the figures a reader looks for first, ahead of the long objects (a truncated log still shows them); filled in below
         out["summary"] = {}
         # the same reads must give the same graph whatever N is (strong scaling and N = 1): the sum of the
@@ -1330,8 +1412,8 @@ def main():
         if not args.no_extras and not args.iid and not args.direct:
             graph.close()
             torch.cuda.empty_cache()
-            osteps = 0 if args.no_cpu_baseline else max(0, min(args.oracle_steps, nsteps))
-            ex = extras(mcx, batches, packed, nsteps, args.table_slots, osteps, not args.no_full_e2e)
+            osteps = 0 if args.no_cpu_baseline else max(0, min(args.oracle_steps, nres))
+            ex = extras(mcx, batches, packed, nres, args.table_slots, osteps, not args.no_full_e2e)
             for key in ("host_fed", "e2e", "e2e_full", "default_defer", "ascii_resident", "packed_resident", "other_configs", "inprocess_2_shards_1gpu", "inprocess_8_shards_1gpu"):
                 if key in ex:
                     out[key] = ex[key]

@@ -52,28 +52,49 @@ def test_capacity_kats_of_the_reference(host, orc):
 
 
 def test_constants_and_memory_formula_of_the_reference_header(host, orc):
-    """src/basic/hash_mem.h compiled unmodified into oracle/_ref: REHASH_LIMIT and MAX_BUCKET_SIZE against the oracle's,
-    ht_mem() against the bytes the product's sizing reports, the occupancy thresholds `build` warns at
+    """src/basic/hash_mem.h compiled unmodified into oracle/_ref (its answers stored in tests/golden/reference_vectors.npz
+    by tests/golden/make_ref_vectors.py; checked live as well when oracle/_ref is built): REHASH_LIMIT and MAX_BUCKET_SIZE
+    against the oracle's, ht_mem() against the bytes the product's sizing reports, the occupancy thresholds `build` warns at
     (cmd_mem.c:66, ctx_build.c) against the literals the host program uses."""
+    import numpy as np
+    import struct
+    vec = np.load(os.path.join(ROOT, "tests", "golden", "reference_vectors.npz"))
+    f32 = lambda bits: struct.unpack("<f", struct.pack("<I", int(bits)))[0]
+    rehash, max_bucket, ideal, warn = (int(x) for x in vec["hashmem_const"])
+    ideal, warn = f32(ideal), f32(warn)
     R = orc.ref_hashmem()
-    if R is None:
-        pytest.skip("oracle/_ref/libhashmemref.so not built (needs /root/reference at build time)")
     L = orc.lib()
-    assert (R.ref_rehash_limit(), R.ref_max_bucket_size()) == (L.orc_rehash_limit(), L.orc_max_bucket_size()) == (20, 48)
-    assert (R.ref_ideal_occupancy(), R.ref_warn_occupancy()) == (0.75, C.c_float(0.9).value)
+    if R is not None:
+        assert (R.ref_rehash_limit(), R.ref_max_bucket_size()) == (rehash, max_bucket)
+        assert (R.ref_ideal_occupancy(), R.ref_warn_occupancy()) == (ideal, warn)
+    assert (rehash, max_bucket) == (L.orc_rehash_limit(), L.orc_max_bucket_size()) == (20, 48)
+    assert (ideal, warn) == (0.75, C.c_float(0.9).value)
     src = open(os.path.join(ROOT, "mccortex_amd", "host", "cmd_build.c")).read()
     assert "#define IDEAL_OCCUPANCY 0.75f" in src and "#define WARN_OCCUPANCY 0.9f" in src
     import random
     rnd = random.Random(3)
+    rows_k, rows_m = iter(vec["hashmem_kmers"]), iter(vec["hashmem_mem"])
     for bits in (104, 168, 288):
         for _ in range(200):
             nk = rnd.randrange(1, 1 << rnd.randrange(4, 40))
             p = host.table_plan_for_kmers(nk, bits)
-            assert 1 <= p.bucket_size <= R.ref_max_bucket_size() + 1   # (hash_mem.c:9-11: floor(n / buckets) <= 48, the bucket takes the ceiling)
-            assert p.bytes == R.ref_ht_mem(p.bucket_size, p.nbuckets, bits)
+            want = [int(x) for x in next(rows_k)]
+            assert want[:2] == [nk, bits]
+            assert 1 <= p.bucket_size <= max_bucket + 1   # (hash_mem.c:9-11: floor(n / buckets) <= 48, the bucket takes the ceiling)
+            # the stored ht_mem is the reference's for this plan: the plan must be the one it was taken on
+            assert (p.bucket_size, p.nbuckets) == (want[2], want[3])
+            assert p.bytes == want[4]
+            if R is not None:
+                assert p.bytes == R.ref_ht_mem(p.bucket_size, p.nbuckets, bits)
         for mem in (1 << 20, 512 << 20, 70 << 30):
             p = host.table_plan_for_memory(mem, bits)
-            assert p.bytes == R.ref_ht_mem(p.bucket_size, p.nbuckets, bits) <= mem
+            want = [int(x) for x in next(rows_m)]
+            assert want[:2] == [mem, bits]
+            assert (p.bucket_size, p.nbuckets) == (want[2], want[3])
+            assert p.bytes == want[4] <= mem
+            if R is not None:
+                assert p.bytes == R.ref_ht_mem(p.bucket_size, p.nbuckets, bits)
+    assert next(rows_k, None) is None and next(rows_m, None) is None
 
 
 def test_memory_limit_fills_but_never_exceeds(host):

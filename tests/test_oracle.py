@@ -11,6 +11,10 @@ import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 KATS = json.load(open(os.path.join(HERE, "golden", "reference_kats.json")))
+# what the reference's lookup3.h / kmer_hash.h / revcmp.c answered for the fixed inputs of the tests below
+# (tests/golden/make_ref_vectors.py, from oracle/_ref): the comparisons run without the reference tree, and
+# against the live oracle/_ref libraries as well where build() could compile them
+REFVEC = np.load(os.path.join(HERE, "golden", "reference_vectors.npz"))
 
 
 def _words(x, W):
@@ -38,43 +42,61 @@ def test_kmer_kats(orc, name, k):
         assert _words(key, W) == _words(x, W)
 
 
+def _bkmer(orc, ws):
+    y = orc.BKmer()
+    for i, w in enumerate(ws):
+        y.b[i] = int(w)
+    return y
+
+
+def _kmer_str(orc, ws, k):
+    buf = C.create_string_buffer(160)
+    orc.lib().orc_kmer_to_str(_bkmer(orc, ws), k, buf)
+    return buf.value.decode()
+
+
 def test_hash_matches_reference_lookup3(orc):
     """kmer_hash.h is a fixed-length specialisation of libs/misc/lookup3.h hashlittle: compare
-    the oracle with the reference's own vendored file compiled into oracle/_ref."""
-    R = orc.ref_lookup3()
-    if R is None:
-        pytest.skip("oracle/_ref/liblk3ref.so not built (needs /root/reference at build time)")
+    the oracle with the reference's own vendored file compiled into oracle/_ref (its answers stored in
+    tests/golden/reference_vectors.npz; checked live as well when oracle/_ref is built)."""
     L = orc.lib()
-    rng = np.random.default_rng(1)
+    R = orc.ref_lookup3()
     for k in (3, 15, 31, 33, 47, 63, 65, 95, 127):
         W = L.orc_words_for_k(k)
-        for _ in range(200):
-            x = L.orc_kmer_from_str(_rand_kmer(rng, k).encode(), k)
-            iv = int(rng.integers(0, 2**32))
-            a = np.array(_words(x, W), dtype=np.uint64)
-            assert L.orc_kmer_hash(x, k, iv) == R.ref_lk3_hashlittle(a.ctypes.data, 8 * W, iv)
+        rows = REFVEC["lk3_k%d" % k]
+        assert rows.shape == (200, W + 2)
+        for row in rows:
+            ws, iv, want = [int(w) for w in row[:W]], int(row[W]), int(row[W + 1])
+            x = L.orc_kmer_from_str(_kmer_str(orc, ws, k).encode(), k)
+            assert _words(x, W) == ws
+            assert L.orc_kmer_hash(x, k, iv) == want
+            if R is not None:
+                a = np.array(ws, dtype=np.uint64)
+                assert R.ref_lk3_hashlittle(a.ctypes.data, 8 * W, iv) == want
 
 
 @pytest.mark.parametrize("k", [3, 15, 29, 31, 33, 47, 63, 65, 79, 95, 97, 111, 127])
 def test_hash_matches_reference_kmer_hash_h(orc, mcx, k):
     """The reference's own BinaryKmer hash -- bklk3_hashlittle, src/kmer/kmer_hash.h:162-211, compiled unmodified
-    into oracle/_ref with NUM_BKMER_WORDS = 1 .. 4 -- against the oracle's orc_kmer_hash and the product's host
+    into oracle/_ref with NUM_BKMER_WORDS = 1 .. 4 (its answers stored in tests/golden/reference_vectors.npz; checked
+    live as well when oracle/_ref is built) -- against the oracle's orc_kmer_hash and the product's host
     template mcx_kmer_hash (the device uses the same template: mcx_kmer.h kmer_hash<W>), on canonical keys and
     arbitrary seeds (hash_table.c:132-145 rehashes with seed + i)."""
     L = orc.lib()
     W = L.orc_words_for_k(k)
     R = orc.ref_revcmp(W)
-    if R is None or not hasattr(R, "ref_bklk3_hashlittle"):
-        pytest.skip("oracle/_ref/librevcmp%d.so with kmer_hash.h not built (needs /root/reference at build time)" % W)
-    rng = np.random.default_rng(500 + k)
-    for s in [_rand_kmer(rng, k) for _ in range(300)] + ["A" * k, "T" * k, "ACG" * (k // 3) + "A" * (k % 3)]:
-        x = L.orc_kmer_from_str(s.encode(), k)
-        key = L.orc_kmer_get_key(x, k)
-        a = np.array(_words(key, W), dtype=np.uint64)
-        for iv in (0, 1, 7, int(rng.integers(0, 2**32))):
-            want = R.ref_bklk3_hashlittle(a.ctypes.data, iv)
-            assert L.orc_kmer_hash(key, k, iv) == want
-            assert mcx.kmer_hash([int(w) for w in a], k, iv) == want
+    R = R if R is not None and hasattr(R, "ref_bklk3_hashlittle") else None
+    rows = REFVEC["bklk3_k%d" % k]
+    assert rows.shape == (303 * 4, W + 2)
+    for row in rows:
+        ws, iv, want = [int(w) for w in row[:W]], int(row[W]), int(row[W + 1])
+        key = L.orc_kmer_get_key(L.orc_kmer_from_str(_kmer_str(orc, ws, k).encode(), k), k)
+        assert _words(key, W) == ws
+        a = np.array(ws, dtype=np.uint64)
+        if R is not None:
+            assert R.ref_bklk3_hashlittle(a.ctypes.data, iv) == want
+        assert L.orc_kmer_hash(key, k, iv) == want
+        assert mcx.kmer_hash([int(w) for w in a], k, iv) == want
 
 
 @pytest.mark.parametrize("k", list(range(3, 128, 2)))
@@ -82,34 +104,34 @@ def test_revcomp_matches_reference_revcmp(orc, mcx, k):
     """orc_kmer_revcomp / orc_kmer_get_key and the product's host template mcx_kmer_canonical against
     the reference's own code: dev/bkmer_revcmp/revcmp.c (all four binary_kmer_reverse_complement{1..4};
     number 2 is src/graph/binary_kmer.c:102-133 line for line), compiled unmodified with
-    NUM_BKMER_WORDS = 1 .. 4 into oracle/_ref.  Pins the b[0]-is-the-top-word layout, the base order
+    NUM_BKMER_WORDS = 1 .. 4 into oracle/_ref (its answers stored in tests/golden/reference_vectors.npz; checked
+    live as well when oracle/_ref is built).  Pins the b[0]-is-the-top-word layout, the base order
     inside a word and the shift across words for every odd k up to 127 (mccortex95 / mccortex127)."""
     L = orc.lib()
     W = L.orc_words_for_k(k)
     R = orc.ref_revcmp(W)
-    if R is None:
-        pytest.skip("oracle/_ref/librevcmp%d.so not built (needs /root/reference at build time)" % W)
-    rng = np.random.default_rng(100 + k)
     comp = {"A": "T", "C": "G", "G": "C", "T": "A"}
     buf = C.create_string_buffer(160)
-    cases = [_rand_kmer(rng, k) for _ in range(60)] + ["A" * k, "T" * k, "C" * k, "G" * k, "AC" * (k // 2) + "G"]
-    for s in cases:
+    rows = REFVEC["revcmp_k%d" % k]
+    assert rows.shape == (65, 2 * W)
+    fixed = ["A" * k, "T" * k, "C" * k, "G" * k, "AC" * (k // 2) + "G"]
+    for i, row in enumerate(rows):
+        fw_stored, want = [int(w) for w in row[:W]], [int(w) for w in row[W:]]
+        s = _kmer_str(orc, fw_stored, k)
+        if i >= 60:
+            assert s == fixed[i - 60]
         x = L.orc_kmer_from_str(s.encode(), k)
-        a = np.array(_words(x, W), dtype=np.uint64)
-        want = None
-        for method in (1, 2, 3, 4):
-            out = np.zeros(W, dtype=np.uint64)
-            R.ref_revcmp(method, a.ctypes.data, k, out.ctypes.data)
-            got = [int(w) for w in out]
-            assert want is None or got == want  # the reference's four variants agree with each other
-            want = got
+        assert _words(x, W) == fw_stored
+        a = np.array(fw_stored, dtype=np.uint64)
+        if R is not None:
+            for method in (1, 2, 3, 4):  # the reference's four variants agree with each other and with the stored answer
+                out = np.zeros(W, dtype=np.uint64)
+                R.ref_revcmp(method, a.ctypes.data, k, out.ctypes.data)
+                assert [int(w) for w in out] == want
         rc = L.orc_kmer_revcomp(x, k)
         assert _words(rc, W) == want
         # ... and the words the reference code produced spell the reverse complement
-        y = orc.BKmer()
-        for i in range(W):
-            y.b[i] = want[i]
-        L.orc_kmer_to_str(y, k, buf)
+        L.orc_kmer_to_str(_bkmer(orc, want), k, buf)
         assert buf.value.decode() == "".join(comp[c] for c in reversed(s))
         # canonical key = the smaller of the two, word 0 (the top word) first (binary_kmer.c:43-57)
         fw = _words(x, W)
