@@ -307,6 +307,21 @@ int mcx_graph_add_records(mcx_graph *g, const void *recs, uint64_t nrecs, int fi
  * db_graph_intersect_edges, src/graph/db_graph.c:630-673).  *removed = k-mers dropped. */
 int mcx_graph_intersect_finish(mcx_graph *g, uint64_t *removed);
 
+/* `inferedges`: infer_kmer_edges (src/tools/infer_edges.c) for every record of `recs` (.ctx body
+ * layout, ncols == the graph's colours) against the k-mers loaded into the graph.  Each edge that some
+ * colour lacks (default, --all) or that some colour has and another lacks (MCX_INFER_POP, --pop)
+ * names a neighbour k-mer; where the neighbour is in the graph and present in colour c, and the
+ * record has coverage in c, the edge is added to colour c of the record.  Present means a non-zero
+ * value in c (coverage or edges: node_in_cols of a file, graphs_load.c:151-154), or coverage > 0 with
+ * MCX_INFER_PRESENCE_COVG (a stream, infer_edges.c:_add_edge_to_colours).  The records' edge bytes
+ * are updated in place; *nmodified = records whose edges changed.  The table is only read.  Not for
+ * a graph split over devices or in intersect mode.
+ * mcx_graph_infer_edges streams host records through two device buffers (copies overlap the
+ * kernel; MCX_INFER_CHUNK=<records> caps the chunk); mcx_graph_infer_edges_dev takes records in HBM. */
+enum { MCX_INFER_POP = 1, MCX_INFER_PRESENCE_COVG = 2 };
+int mcx_graph_infer_edges(mcx_graph *g, void *recs, uint64_t nrecs, int ncols, uint32_t flags, uint64_t *nmodified);
+int mcx_graph_infer_edges_dev(mcx_graph *g, void *d_recs, uint64_t nrecs, int ncols, uint32_t flags, uint64_t *nmodified);
+
 /* Table scans (imply a sync).
  * mcx_graph_kmer_covg       db_graph_get_kmer_covg (src/graph/db_graph.c:490-534): per colour, the
  *                           number of k-mers with coverage and their summed coverage (ncols entries)

@@ -28,6 +28,7 @@
 #include "mcx_superk.h"
 #include "mcx_streamfc.h"
 #include "mcx_ubench.h"
+#include "mcx_infer.h"
 
 using namespace mcx;
 
@@ -262,6 +263,7 @@ struct mcx_graph {
   int gidx = 0;
   mcx_group *as_group = nullptr;
   uint32_t own_lbo = 0;  // > 0: a shard of a group that deals the keys out by minimizer (exchange format v3): log2 shards
+  unsigned long long *d_infer = nullptr;  // inferedges: [records modified, lookups] of the current call
 };
 
 // how the kernels that walk records / reads on every shard tell their own keys (mcx_kernels.h: OwnerSpec)
@@ -484,6 +486,7 @@ extern "C" void mcx_graph_destroy(mcx_graph *g)
   }
   if (g->d_ctr) (void)hipFree(g->d_ctr);
   if (g->d_readstrt) (void)hipFree(g->d_readstrt);
+  if (g->d_infer) (void)hipFree(g->d_infer);
   if (g->h_ctr) (void)hipHostFree(g->h_ctr);
   if (g->h_full) (void)hipHostFree(g->h_full);
   if (g->h_snap) {
@@ -2994,6 +2997,120 @@ extern "C" int mcx_graph_add_records(mcx_graph *g, const void *recs, uint64_t nr
   if (h_st.first_oversized != ~0ULL)
     return fail(MCX_ERR_ARG, "oversized kmer in record %llu [kmer: %d]", (unsigned long long)h_st.first_oversized, g->k);
   return MCX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// inferedges (ctx_infer_edges.c, infer_edges.c): records against the loaded table, mcx_infer.h
+// ---------------------------------------------------------------------------
+// The checks both entries share; on success every insert has landed (the table is read-only from here)
+// and the call's counters are zeroed.
+static int infer_begin(mcx_graph *g, const void *recs, uint64_t nrecs, int ncols, uint32_t flags)
+{
+  if (!g) return fail(MCX_ERR_ARG, "null graph");
+  if (g->as_group || g->group || g->t.lbo || g->own_lbo)
+    return fail(MCX_ERR_ARG, "inferedges needs the whole table on one device, not a graph split over devices");
+  if (g->hidden >= 0) return fail(MCX_ERR_ARG, "inferedges does not take a graph in intersect mode");
+  if (ncols != g->ncols) return fail(MCX_ERR_ARG, "the records have %d colours, the graph %d", ncols, g->ncols);
+  if (flags & ~(uint32_t)(MCX_INFER_POP | MCX_INFER_PRESENCE_COVG)) return fail(MCX_ERR_ARG, "unknown inferedges flags 0x%x", flags);
+  if (!infer_tile_recs(8u * g->W + 5u * (uint32_t)ncols)) return fail(MCX_ERR_ARG, "too many colours for inferedges: %d", ncols);
+  if (nrecs && !recs) return fail(MCX_ERR_ARG, "null records");
+  HIP_TRY(hipSetDevice(g->device));
+  int rc = fetch_counters(g);
+  if (rc != MCX_OK) return rc;
+  if (!g->d_infer) HIP_TRY(hipMalloc((void **)&g->d_infer, 2 * sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(g->d_infer, 0, 2 * sizeof(unsigned long long), g->stream));
+  return MCX_OK;
+}
+
+static int infer_launch(mcx_graph *g, void *d_recs, uint64_t n, uint32_t flags)
+{
+  const uint32_t rec_bytes = 8u * g->W + 5u * (uint32_t)g->ncols, R = infer_tile_recs(rec_bytes);
+  const unsigned grid = (unsigned)std::min<uint64_t>((n + R - 1) / R, (uint64_t)g->grid);
+  if (!grid) return MCX_OK;
+  SpanGuard sp(g, "k_infer_records");
+  LAUNCH_W4(g->W, k_infer_records, dim3(grid), dim3(kInferThreads), infer_lds_bytes(rec_bytes), g->stream, g->t,
+            (uint8_t *)d_recs, n, (uint32_t)g->ncols, g->k, flags, g->d_infer);
+  HIP_TRY(hipGetLastError());
+  return MCX_OK;
+}
+
+static int infer_end(mcx_graph *g, uint64_t *nmodified)
+{
+  unsigned long long h[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(h, g->d_infer, sizeof(h), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  if (nmodified) *nmodified = h[0];
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_infer_edges_dev(mcx_graph *g, void *d_recs, uint64_t nrecs, int ncols, uint32_t flags,
+                                         uint64_t *nmodified)
+{
+  int rc = infer_begin(g, d_recs, nrecs, ncols, flags);
+  if (rc == MCX_OK) rc = infer_launch(g, d_recs, nrecs, flags);
+  if (rc == MCX_OK) rc = infer_end(g, nmodified);
+  return rc;
+}
+
+// Host records stream through two staging pairs: chunk i is uploaded on the copy stream while the kernel of
+// chunk i - 1 runs, and chunk i - 1 is copied back while the kernel of chunk i runs.
+static uint64_t infer_chunk_recs(const mcx_graph *g, uint64_t rec_bytes)
+{
+  uint64_t n = std::max<uint64_t>(1, std::min<uint64_t>(kStageBytes, g->stage_alloc) / rec_bytes);
+  const char *e = getenv("MCX_INFER_CHUNK");  // records per chunk (tests of the chunk seams)
+  if (e && strtoull(e, nullptr, 10) > 0) n = std::min<uint64_t>(n, strtoull(e, nullptr, 10));
+  return n;
+}
+
+extern "C" int mcx_graph_infer_edges(mcx_graph *g, void *recs, uint64_t nrecs, int ncols, uint32_t flags, uint64_t *nmodified)
+{
+  int rc = infer_begin(g, recs, nrecs, ncols, flags);
+  if (rc == MCX_OK) rc = ensure_stage(g);
+  if (rc != MCX_OK) return rc;
+  HIP_TRY(hipStreamSynchronize(g->stream));  // the staging buffers are ours now
+  HIP_TRY(hipStreamSynchronize(g->cstream));
+  uint8_t *h = (uint8_t *)recs;
+  const uint64_t rb = 8ull * g->W + 5ull * (uint64_t)ncols, per_chunk = infer_chunk_recs(g, rb);
+  uint64_t at[2] = {0, 0}, cnt[2] = {0, 0};
+  bool back[2] = {false, false};  // the copy back of buffer b is queued and its records not yet returned
+  int prev = -1;                  // buffer whose kernel is queued and whose copy back is not
+  auto queue_back = [&](int b) -> int {
+    HIP_TRY(hipStreamWaitEvent(g->cstream, g->ev[b], 0));
+    HIP_TRY(hipMemcpyAsync(g->h_stage[b], g->d_stage[b], cnt[b] * rb, hipMemcpyDeviceToHost, g->cstream));
+    HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
+    back[b] = true;
+    return MCX_OK;
+  };
+  auto take_back = [&](int b) -> int {
+    HIP_TRY(hipEventSynchronize(g->ev_copy[b]));
+    memcpy(h + at[b] * rb, g->h_stage[b], cnt[b] * rb);
+    back[b] = false;
+    return MCX_OK;
+  };
+  uint64_t i = 0;
+  for (uint64_t r0 = 0; r0 < nrecs && rc == MCX_OK; r0 += per_chunk, i++) {
+    const int b = (int)(i & 1);
+    if (back[b] && (rc = take_back(b)) != MCX_OK) break;
+    at[b] = r0;
+    cnt[b] = std::min(per_chunk, nrecs - r0);
+    memcpy(g->h_stage[b], h + r0 * rb, cnt[b] * rb);
+    HIP_TRY(hipMemcpyAsync(g->d_stage[b], g->h_stage[b], cnt[b] * rb, hipMemcpyHostToDevice, g->cstream));
+    HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
+    HIP_TRY(hipStreamWaitEvent(g->stream, g->ev_copy[b], 0));
+    if ((rc = infer_launch(g, g->d_stage[b], cnt[b], flags)) != MCX_OK) break;
+    HIP_TRY(hipEventRecord(g->ev[b], g->stream));
+    if (prev >= 0) rc = queue_back(prev);
+    prev = b;
+  }
+  if (rc == MCX_OK && prev >= 0) rc = queue_back(prev);
+  for (int b = 0; b < 2 && rc == MCX_OK; b++)
+    if (back[b]) rc = take_back(b);
+  if (rc != MCX_OK) {  // leave nothing in flight on the staging buffers
+    (void)hipStreamSynchronize(g->stream);
+    (void)hipStreamSynchronize(g->cstream);
+    return rc;
+  }
+  return infer_end(g, nmodified);
 }
 
 // ---------------------------------------------------------------------------

@@ -21,6 +21,7 @@ SYMBOLS = [
     "mcx_graph_nkmers", "mcx_graph_device_stats", "mcx_graph_stream", "mcx_graph_export",
     "mcx_kmer_from_str", "mcx_kmer_canonical", "mcx_kmer_hash", "mcx_pack_bases", "mcx_pack_reads_host", "mcx_pack_stream_dev", "mcx_graph_add_packed_dev",
     "mcx_ubench_stream", "mcx_ubench_random_rmw", "mcx_graph_insert_stats", "mcx_multi_exchange_bytes", "mcx_graph_hashtest", "mcx_hashtest_func", "mcx_debug_probe",
+    "mcx_graph_infer_edges", "mcx_graph_infer_edges_dev",
 ]
 
 
@@ -54,6 +55,7 @@ class RecordStats(C.Structure):
 
 
 RECORDS_MUST_EXIST = 1
+INFER_POP, INFER_PRESENCE_COVG = 1, 2
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 
 
@@ -92,6 +94,8 @@ def lib():
     L.mcx_sort_records.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_int]
     L.mcx_records_sorted.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
     L.mcx_graph_intersect_finish.argtypes = [vp, u64p]
+    L.mcx_graph_infer_edges.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, u64p]
+    L.mcx_graph_infer_edges_dev.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, u64p]
     L.mcx_superk_supported.argtypes = [C.c_int]
     L.mcx_superk_record_bytes.argtypes = [C.c_int]
     L.mcx_superk_owner.restype = C.c_uint32
@@ -306,6 +310,29 @@ class Graph:
         _check(self.L.mcx_graph_add_records(self.h, _ptr(recs), recs.size // rs, file_ncols, _ptr(frm), _ptr(into),
                                             len(frm), (RECORDS_MUST_EXIST if must_exist else 0) | (2 if mask_edges else 0), C.byref(st)))
         return st
+
+    def _infer_flags(self, pop, presence):
+        if presence not in ("any", "covg"):
+            raise ValueError("presence must be 'any' (a file: coverage or edges) or 'covg' (a stream)")
+        return (INFER_POP if pop else 0) | (INFER_PRESENCE_COVG if presence == "covg" else 0)
+
+    def infer_edges(self, recs, pop=False, presence="any"):
+        """`inferedges` over .ctx body bytes (self.ncols colours) against the loaded graph:
+        returns (the records with the inferred edges added, number of records modified)"""
+        a = np.frombuffer(bytes(recs), dtype=np.uint8).copy()
+        rs = 8 * self.W + 5 * self.ncols
+        assert a.size % rs == 0
+        n = C.c_uint64(0)
+        _check(self.L.mcx_graph_infer_edges(self.h, _ptr(a), a.size // rs, self.ncols, self._infer_flags(pop, presence),
+                                            C.byref(n)))
+        return a.tobytes(), int(n.value)
+
+    def infer_edges_dev(self, d_recs, nrecs, pop=False, presence="any"):
+        """the same over records already in HBM (a device pointer or tensor), updated in place; returns records modified"""
+        n = C.c_uint64(0)
+        _check(self.L.mcx_graph_infer_edges_dev(self.h, _ptr(d_recs), int(nrecs), self.ncols, self._infer_flags(pop, presence),
+                                                C.byref(n)))
+        return int(n.value)
 
     def kmer_covg(self):
         """per colour: (k-mers with coverage, summed coverage) -- db_graph_get_kmer_covg"""
