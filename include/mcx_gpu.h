@@ -116,7 +116,18 @@ int mcx_graph_reset(mcx_graph *g);
  *   "prepare"      allocate now what the first mcx_graph_add_reads otherwise allocates (pinned staging
  *                  buffers, the partition workspace): lets a host that parses with other threads hide
  *                  ~0.1 s behind the parse of its first batch
- *   "profile"      1: time every kernel launch with HIP events (see mcx_graph_profile) */
+ *   "profile"      1: time every kernel launch with HIP events (see mcx_graph_profile)
+ * Test and experiment knobs (launch geometry only: no allocation depends on them, so they may be set at any
+ * time and take effect from the next launch; the answers must not change with them):
+ *   "grid"         n >= 1: at most n blocks for the grid-stride launches that otherwise take CUs x 8 (the stream
+ *                  k-merisers k_stream / k_stream_bin / k_stream_superk, k_insert_tuples, k_infer_records, the
+ *                  table scans, the export compaction) and 4 n for the split, the LDS insert and k_superk_bin
+ *                  unless "grid_split" / "grid_insert" are set; 0 restores CUs x 8.  Small grids make every
+ *                  block walk several tiles, which the byte-exact tests use to reach the kernels' loops.
+ *   "grid_stream"  n >= 1: blocks of k_stream_bin (0: "grid"; MCX_GRID_STREAM at creation)
+ *   "grid_split"   n >= 1: blocks of the split k_tuples_bin (0: 4 x "grid", halved / quartered for its 512- /
+ *                  1024-thread forms; MCX_GRID_SPLIT)
+ *   "grid_insert"  n >= 1: blocks of k_lds_insert (0: 4 x "grid"; MCX_GRID_INSERT) */
 int mcx_graph_configure(mcx_graph *g, const char *key, uint64_t value);
 /* "kernel calls total_ms" per line for the launches recorded since "profile" was set. */
 int mcx_graph_profile(mcx_graph *g, char *buf, size_t buflen);

@@ -1375,6 +1375,13 @@ extern "C" int mcx_graph_configure(mcx_graph *g, const char *key, uint64_t value
               g->l1_keys ? (double)g->nsets * g->b1 * g->rep1 * g->cap1 * 8 * g->W / 1e9 : 0.0, (t2 - t1) * 1e3, (now_s() - t2) * 1e3);
     return rc;
   }
+  if (!strcmp(key, "grid")) {  // test knob: n caps the grid-stride launches at n blocks (the split / insert at 4 n); 0 = CUs x 8
+    if (value > (1u << 20)) return fail(MCX_ERR_ARG, "grid: 0 .. 2^20 blocks");
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device));
+    g->grid = value ? (int)value : cus * 8;  // (launches only: nothing is allocated per block of g->grid)
+    return MCX_OK;
+  }
   if (!strcmp(key, "grid_stream")) { g->grid_stream = (int)value; return MCX_OK; }
   if (!strcmp(key, "grid_split")) { g->grid_split = (int)value; return MCX_OK; }
   if (!strcmp(key, "grid_insert")) { g->grid_insert = (int)value; return MCX_OK; }
