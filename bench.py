@@ -6,15 +6,21 @@ Workload (BASELINE.json configs[1], "C2"): k=31, 1 colour, synthetic 150 bp read
 2^30 slots.  One step = one batch of 5,000,000 reads (600M k-mer occurrences) that is already
 resident in HBM as a '\\n'-separated ASCII byte stream (`value`: the 2-bit packing of the bases is
 INSIDE the clock -- the kernel encodes the ASCII bytes in its tile prologue; parse and H2D are outside:
-see `host_fed` and `e2e`); 10 steps are the 50M x 150bp set.  The same run also reports, as separate objects of the
-JSON line: `host_fed` (the same reads handed over in host memory: staging + PCIe inside the clock),
+see `host_fed` and `e2e`); 10 steps are the 50M x 150bp set.
+
+A plain run does only what `value` needs: it builds, makes the reads, warms up, times the steps, writes `--dump-outputs`
+if asked, and prints the JSON line (`value`, `ms_per_step`, the graph checksum, the pipeline-level roofline of the timed
+region and its HIP-event spans).  `--full` adds everything else, each part in runs of its own.  At N = 1 these are
+separate objects of the JSON line: `host_fed` (the same reads handed over in host memory: staging + PCIe inside the clock),
 `e2e` (`mccortex31 build --sort` on a FASTQ file of the same shape: process start, parse, build, sort,
 .ctx write), `default_defer` (the library's own flush size instead of the bench's), `other_configs`
 (C4: k=63; C5-like: 4 colours; C2-stress: iid reads; `hashtest`: the reference's own published table benchmark),
 `e2e_full` (the CLI on the whole 50M x 150bp FASTQ) and `cpu_baseline` (the oracle on the host cores, on the SAME
 reads and the same `-n 1G` table; its records' checksum must equal the GPU graph's: `config.checksum_matches_oracle`).
-`roofline` carries the device's MEASURED ceilings (streaming copy, random 64-byte-sector RMW over a table-sized
-working set: mcx_ubench_*) next to the nominal 8 TB/s, and per-kernel durations from a second, non-overlapped pass.
+`roofline` then also carries the device's MEASURED ceilings (streaming copy, random 64-byte-sector RMW over a
+table-sized working set: mcx_ubench_*) next to the nominal 8 TB/s, and per-kernel durations from a second,
+non-overlapped pass over the timed steps.
+`--no-extras`, `--no-cpu-baseline` and `--no-full-e2e` leave parts out of a `--full` run.
 
 N>1 (one process per GPU, torchrun).  Default `--scaling strong` = BASELINE config C3: the SAME reads
 as N=1 (step i is the same 5M-read batch, every rank takes reads [r B/N, (r+1) B/N) of it), the same
@@ -23,7 +29,8 @@ checksums must equal the N=1 `graph_checksum` (`config.checksum_matches_n1`).  `
 rank takes its own 5M-read batch per step (genome scaled to N x 200 Mbp, 2^30 slots per GPU).  Either
 way a rank cuts its reads into per-owner super-k-mer records (owner = hash of the k-mer's canonical
 minimizer), exchanges them with RCCL all-to-alls and k-merises + inserts what it owns (exchange
-format v3).
+format v3).  Both exchange formats are timed, since `value` is the faster one; `--full` adds
+the C5 pass (4 colours) and the C ABI's one-process driver over the same GPUs.
 """
 import argparse
 import json
@@ -928,7 +935,7 @@ def inprocess_multi(args):
 
 def sharded_main(mcx, shard, dist, args, device, local_rank, rank, world, force_shard):
     """N > 1 (one process per GPU; also N = 1 under MCX_BENCH_FORCE_SHARD=1): the exchange path in BOTH formats on one
-    colour, then config C5 (4 colours) in the faster one, then the C ABI's one-process driver as a subprocess.
+    colour; with --full, then config C5 (4 colours) in the faster one and the C ABI's one-process driver as a subprocess.
     `value` is the better one-colour figure; everything else sits in `config`."""
     B, nsteps, nwarm = args.batch_reads, args.steps, args.warmup
     strong = args.scaling == "strong" and not args.iid
@@ -975,7 +982,7 @@ def sharded_main(mcx, shard, dist, args, device, local_rank, rank, world, force_
                                 [(0, x) for x in x_timed], [(0, x) for x in x_warm], xmax, slots_per_gpu, nsteps)
     best = max(one, key=lambda f: one[f]["value"])
     c5 = None
-    if not args.iid and os.environ.get("MCX_BENCH_C5", "1") != "0":
+    if args.full and not args.iid and os.environ.get("MCX_BENCH_C5", "1") != "0":
         c5_timed = _deal_colours(batches[:nsteps], (B * rank // world) if strong else 0, B, 4, xmax, shard, dist, world, device)
         c5_warm = [(i % 4, x) for i, x in enumerate(x_warm)]
         c5 = sharded_pass(mcx, shard, dist, args, device, local_rank, rank, world, best, 4, c5_timed, c5_warm, xmax, slots_per_gpu, nsteps)
@@ -1024,7 +1031,7 @@ def sharded_main(mcx, shard, dist, args, device, local_rank, rank, world, force_
         cfg["C5"] = c5
     # the C ABI's one-process driver over the same devices (bounded subprocess; rank 0 only, the other ranks have
     # released their memory and wait at the closing barrier)
-    if world > 1 and strong and shard.dist_backend() == "nccl" and os.environ.get("MCX_BENCH_INPROCESS", "1") != "0":
+    if args.full and world > 1 and strong and shard.dist_backend() == "nccl" and os.environ.get("MCX_BENCH_INPROCESS", "1") != "0":
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--inprocess-multi", str(world), "--steps", str(nsteps), "--warmup", str(min(nwarm, 1)),
                "--batch-reads", str(B), "--table-slots", str(args.table_slots), "--genome", str(args.genome), "--err", str(args.err),
@@ -1139,15 +1146,19 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch-reads", type=int, default=BATCH_READS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the device-resident figure (profiling passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything else as well: N = 1: the device's ceilings, per-kernel durations from a "
+                         "non-overlapped pass, host_fed, e2e, e2e_full, the other configs, the in-process shards, cpu_baseline; "
+                         "N > 1: C5 and the one-process driver.  Without it a run does only what `value` needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the device-resident figure, its ceilings and per-kernel pass (profiling passes)")
     ap.add_argument("--oracle-steps", type=int, default=5,
-                    help="steps of the workload the CPU oracle builds into the same -n table (timed = cpu_baseline.value; its records' checksum "
+                    help="with --full: steps of the workload the CPU oracle builds into the same -n table (timed = cpu_baseline.value; its records' checksum "
                          "is compared with the GPU graph of the same steps).  About 20 s of 32 host threads per step; 10 = the whole 50M-read set")
-    ap.add_argument("--no-full-e2e", action="store_true", help="skip e2e_full (the CLI on the whole 50M-read FASTQ: a 15 GB scratch file)")
+    ap.add_argument("--no-full-e2e", action="store_true", help="with --full: skip e2e_full (the CLI on the whole 50M-read FASTQ: a 15 GB scratch file)")
     ap.add_argument("--input", choices=("packed", "ascii"), default="ascii",
                     help="form of the resident stream: ASCII (default: the 2-bit packing is inside the clock), or the packed "
-                         "form the host entry stages (2-bit codes + invalid flags; reported as packed_resident by default)")
+                         "form the host entry stages (2-bit codes + invalid flags; reported as packed_resident by --full)")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="N > 1: strong = the same reads and the same total table as N = 1 (config C3); weak = per-GPU work fixed")
     ap.add_argument("--table-slots", type=int, default=TABLE_SLOTS, help="experiments only")
@@ -1249,8 +1260,8 @@ def main():
     torch.cuda.empty_cache()  # hand the generator's temporaries back before the graph allocates
 
     slots_per_gpu = args.table_slots
-    # the device's streaming and random-RMW ceilings, measured in this run
-    ceil = ceilings(mcx, slots_per_gpu * 16)
+    # the device's streaming and random-RMW ceilings, measured in this run (--full)
+    ceil = ceilings(mcx, slots_per_gpu * 16) if args.full else {}
     graph = mcx.Graph(K, 1, slots_per_gpu, device=local_rank)
     if args.direct:
         graph.configure("defer", 0)
@@ -1302,9 +1313,9 @@ def main():
     # Per-kernel durations that mean something: with the flush overlap on (the default, and what `value` is
     # measured with) the insert of one region group runs beside the split of the next, and the HIP-event spans
     # of the two kernels contain each other.  A second pass over the same steps with the overlap off gives
-    # isolated durations (one kernel at a time on one stream); roofline.kernels / roofline.dominant use those.
+    # isolated durations (one kernel at a time on one stream); roofline.kernels / roofline.dominant use those (--full).
     prof_iso, gpu_ms_iso = None, None
-    if not args.direct:
+    if args.full and not args.direct:
         graph.reset()
         graph.configure("flush_overlap", 0)
         fence()
@@ -1356,25 +1367,17 @@ def main():
         if not args.iid and B == BATCH_READS and args.genome == GENOME_PER_GPU and args.err == 0.001 and READ_LEN == 150 and nsteps in N1_CHECKSUMS:
             out["config"]["checksum_matches_n1"] = ("%016x" % cs_total) == N1_CHECKSUMS[nsteps]
         gpu_ms = ev0.elapsed_time(ev1)
-        kprof = prof_iso if prof_iso is not None else prof  # isolated durations where they exist
-        dom = max(kprof, key=lambda n: kprof[n][1])
-        calls, tot_ms = kprof[dom]
-        avg_ms = tot_ms / calls
         # ROOFLINE, as SURVEY.md 8(d) defines it: algorithmic bytes of the path -- 21.25 B per k-mer occurrence
         # (1.25 input + 8 key read + 8 coverage RMW + ~4 edge RMW) + 8 B per novel key -- over the GPU time of
         # the whole timed region (HIP events on the handle's stream), against 8 TB/s.  The path is three kernels
-        # of comparable length, so the figure is taken over all of them; each kernel's own design bytes over its
-        # own time are under `kernels` (dominant kernel: `dominant`).
+        # of comparable length, so the figure is taken over all of them; with --full, each kernel's own design
+        # bytes over its own isolated time are under `kernels` (dominant kernel: `dominant`).
         in_b = (0.375 if use_packed else 1.0) * (READ_LEN + 1) / (READ_LEN - K + 1.0)  # stream bytes per occurrence
-        kalg = dict(KERNEL_ALG_BYTES, k_stream_bin=in_b + 8.0)
-        alg_bytes = kalg[dom] * kmers_local / calls
-        ach = alg_bytes / (avg_ms * 1e-3) / 1e9
         pipe_bytes = ALG_BYTES_PER_KMER * kmers_local + ALG_BYTES_PER_NOVEL * st.num_kmers_novel
         pipe_ach = pipe_bytes / (gpu_ms * 1e-3) / 1e9
-        ktab = kernel_table(kprof, kmers_local, 1, in_b)
         # HBM bytes of the whole path per occurrence from the newest PMC summary taken on these kernel sources
         tr_total, tr_src = 0.0, None
-        for kn in ktab:
+        for kn in (n for n, (c, t) in prof.items() if t > 0):
             t_k, src_k = pmc_traffic(kn, kmers_local)
             if t_k is None:
                 tr_total, tr_src = None, src_k
@@ -1386,16 +1389,28 @@ def main():
                            "what": "SURVEY 8(d): (21.25 B x k-mer occurrences + 8 B x novel keys) / GPU time of the timed region; "
                                    "traffic = PMC HBM bytes of the three kernels over the same region (null: no summary for these sources)",
                            "alg_bytes": pipe_bytes, "gpu_ms": gpu_ms, "alg_bytes_per_kmer": ALG_BYTES_PER_KMER, "alg_bytes_per_novel_key": ALG_BYTES_PER_NOVEL,
-                           "kernels": ktab,
-                           "kernels_what": ("ISOLATED durations: a second pass over the same steps with the flush overlap off (one kernel at a time on one stream, "
-                                            "HIP events around every launch; same graph checksum); their sum is the GPU time of that pass (gpu_ms_isolated_pass), "
-                                            "the timed region itself (gpu_ms) runs with the overlap on") if prof_iso is not None else "HIP-event spans of the timed region",
-                           "gpu_ms_isolated_pass": gpu_ms_iso,
-                           "kernels_sum_ms": round(sum(v["total_ms"] for v in ktab.values()), 3),
-                           "spans_overlapped": {n: {"launches": c, "total_ms": round(t, 3)} for n, (c, t) in prof.items()} if prof_iso is not None else None,
-                           "dominant": {"kernel": dom, "achieved": ach, "frac": ach / HBM_PEAK_GBS, "avg_kernel_ms": avg_ms, "launches": calls,
-                                        "alg_bytes_per_launch": alg_bytes,
-                                        "note": "the kernel with the largest isolated total; its OWN design bytes (stream + packed tuples) over its average isolated launch"}}
+                           "kernels_what": "per-kernel durations: --full (a second pass over the same steps with the flush overlap off); "
+                                           "spans_overlapped = HIP-event spans of the timed region, which contain each other with the overlap on",
+                           "spans_overlapped": None if args.direct else {n: {"launches": c, "total_ms": round(t, 3)} for n, (c, t) in prof.items()}}
+        if prof_iso is not None or args.direct:
+            kprof = prof_iso if prof_iso is not None else prof  # isolated durations where they exist (the direct path has no overlap)
+            dom = max(kprof, key=lambda n: kprof[n][1])
+            calls, tot_ms = kprof[dom]
+            avg_ms = tot_ms / calls
+            kalg = dict(KERNEL_ALG_BYTES, k_stream_bin=in_b + 8.0)
+            alg_bytes = kalg[dom] * kmers_local / calls
+            ach = alg_bytes / (avg_ms * 1e-3) / 1e9
+            ktab = kernel_table(kprof, kmers_local, 1, in_b)
+            out["roofline"].update({
+                "kernels": ktab,
+                "kernels_what": ("ISOLATED durations: a second pass over the same steps with the flush overlap off (one kernel at a time on one stream, "
+                                 "HIP events around every launch; same graph checksum); their sum is the GPU time of that pass (gpu_ms_isolated_pass), "
+                                 "the timed region itself (gpu_ms) runs with the overlap on") if prof_iso is not None else "HIP-event spans of the timed region",
+                "gpu_ms_isolated_pass": gpu_ms_iso,
+                "kernels_sum_ms": round(sum(v["total_ms"] for v in ktab.values()), 3),
+                "dominant": {"kernel": dom, "achieved": ach, "frac": ach / HBM_PEAK_GBS, "avg_kernel_ms": avg_ms, "launches": calls,
+                             "alg_bytes_per_launch": alg_bytes,
+                             "note": "the kernel with the largest isolated total; its OWN design bytes (stream + packed tuples) over its average isolated launch"}})
         out["roofline"].update(ceil)
         if ceil.get("measured_copy_gbs"):
             out["roofline"]["frac_of_measured_copy"] = pipe_ach / ceil["measured_copy_gbs"]
@@ -1409,7 +1424,7 @@ def main():
                                             "peak_source": "mcx_ubench_random_rmw in this run" if ceil.get("measured_random_rmw_per_s") else "profiles/r01_ubench_atomics.log (round 1)",
                                             "ratio": kmers_local / (gpu_ms * 1e-3) / rmw_peak}
         ex = {}
-        if not args.no_extras and not args.iid and not args.direct:
+        if args.full and not args.no_extras and not args.iid and not args.direct:
             graph.close()
             torch.cuda.empty_cache()
             osteps = 0 if args.no_cpu_baseline else max(0, min(args.oracle_steps, nres))
@@ -1417,7 +1432,7 @@ def main():
             for key in ("host_fed", "e2e", "e2e_full", "default_defer", "ascii_resident", "packed_resident", "other_configs", "inprocess_2_shards_1gpu", "inprocess_8_shards_1gpu"):
                 if key in ex:
                     out[key] = ex[key]
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             gref = ex.get("_gpu_oracle_steps")
             out["cpu_baseline"] = cpu_baseline(batches[0], ex.get("_fastq_sample"), batches, gref["steps"] if gref else 0, args.table_slots)
             full = out["cpu_baseline"].get("full_size", {})

@@ -74,14 +74,14 @@ def test_tool_matches_oracle(mcx, orc, tmp_path, k, exchange, world):
 
 
 def test_bench_two_ranks_strong_reproduces_the_single_gpu_graph(mcx, tmp_path):
-    """`python bench.py --gpus 2` AS THE DRIVER TYPES IT -- a plain subprocess, no launcher: bench.py starts its two ranks
-    itself -- on cuda:0 through the test transport.  Strong scaling = BASELINE config C3 (the N = 1 reads dealt out to the
-    ranks, the N = 1 table split 2 ways): one JSON line that times BOTH exchange formats and the C5 pass (4 colours);
+    """`python bench.py --gpus 2 --full` AS THE DRIVER TYPES IT -- a plain subprocess, no launcher: bench.py starts its two
+    ranks itself -- on cuda:0 through the test transport.  Strong scaling = BASELINE config C3 (the N = 1 reads dealt out to
+    the ranks, the N = 1 table split 2 ways): one JSON line that times BOTH exchange formats and the C5 pass (4 colours);
     the sum of the ranks' graph checksums and node counts must be what the N = 1 run of the same steps reports in either
     format, and the coloured graph must be the one a single rank builds."""
     import json
     # (--defer-tuples: two ranks and this pytest process share the one device's HBM here)
-    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--batch-reads", "1000000", "--defer-tuples", "1000000000"]
+    common = ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras", "--batch-reads", "1000000", "--defer-tuples", "1000000000"]
     e = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for v in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(v, None)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 6: environment knobs against the driver's command (20 steps, one table pass, placed bins)
-run() { env "$@" python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+run() { env "$@" python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

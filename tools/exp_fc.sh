@@ -10,7 +10,7 @@ env $ENVX MCX_STREAM_FC=10 timeout 1500 python -m pytest tests/test_gpu_parity.p
 fi
 for cap in ${CAPS:-0 10}; do
   echo "== bench MCX_STREAM_FC=$cap $ENVX" >> $O
-  env $ENVX MCX_STREAM_FC=$cap timeout 600 python bench.py --steps 10 --warmup 1 --no-cpu-baseline --no-extras 2>>$O.err | python -c "
+  env $ENVX MCX_STREAM_FC=$cap timeout 600 python bench.py --steps 10 --warmup 1 --full --no-cpu-baseline --no-extras 2>>$O.err | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-run() { python bench.py --steps 10 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "
+run() { python bench.py --steps 10 --warmup 1 --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('$1', round(d['value']/1e9,1), round(d['ms_per_step'],3), {k:round(v['total_ms'],1) for k,v in d['roofline']['kernels'].items()}, d['config']['graph_checksum'])"; }
 run base

@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 6: launch grids of the split and the insert (blocks), C2 bench, 10 steps
-run() { env "$@" python bench.py --steps 10 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+run() { env "$@" python bench.py --steps 10 --warmup 1 --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

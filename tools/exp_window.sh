@@ -4,7 +4,7 @@
 #        REPS="4 8 16" WINS="8000000000 12420000000" bash tools/exp_window.sh
 for rep in ${REPS:-8}; do
 for w in ${WINS:-8000000000 12420000000 16000000000}; do
-  MCX_REP1=$rep python bench.py --steps 10 --warmup 1 --no-cpu-baseline --no-extras --defer-tuples $w 2>/dev/null | python -c "
+  MCX_REP1=$rep python bench.py --steps 10 --warmup 1 --full --no-cpu-baseline --no-extras --defer-tuples $w 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

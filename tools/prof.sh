@@ -3,7 +3,7 @@
 # Usage: bash tools/prof.sh <tag> [bench args...]
 set -u
 TAG=${1:-r01}; shift || true
-ARGS=${@:---steps 10 --warmup 1 --no-cpu-baseline --no-extras}
+ARGS=${@:---steps 10 --warmup 1 --full --no-cpu-baseline --no-extras}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp

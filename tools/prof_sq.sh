@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp
 for pass in "pmc_sq SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM SQ_INSTS_VALU" "pmc_lds SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VMEM"; do
   set -- $pass; name=$1; shift
-  rocprofv3 --kernel-trace --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/$name.log 2>&1
+  rocprofv3 --kernel-trace --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python $REPO/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/$name.log 2>&1
   python - <<PY
 import csv, collections
 agg = collections.defaultdict(list)

@@ -1,9 +1,10 @@
 #!/bin/bash
 # Run bench.py once per tuning variant in build/variants (on the GPU box); one line per variant with
 # the whole-job rate and every kernel's total time in the timed region.
-# Usage: [STEPS=10] [ONLY="a b"] tools/sweep.sh [extra bench args]
+# Usage: [STEPS=10] [ONLY="a b"] [OUT=build/sweep] tools/sweep.sh [extra bench args]
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+OUT=${OUT:-build/sweep}
+mkdir -p "$OUT"
 shopt -s nullglob
 for so in "" build/variants/lib_*.so; do
   name=${so:-default}
@@ -11,7 +12,7 @@ for so in "" build/variants/lib_*.so; do
     keep=0; for o in $ONLY; do [ "$so" = "build/variants/lib_$o.so" ] && keep=1; done
     [ $keep = 1 ] || continue
   fi
-  MCX_LIB=${so:+$PWD/$so} timeout 600 python bench.py --steps ${STEPS:-10} --warmup 1 --no-cpu-baseline --no-extras "$@" 2>gpurun_out/sweep_last.err | tail -1 | \
+  MCX_LIB=${so:+$PWD/$so} timeout 600 python bench.py --steps ${STEPS:-10} --warmup 1 --full --no-cpu-baseline --no-extras "$@" 2>"$OUT/sweep_last.err" | tail -1 | \
     python -c "
 import sys,json
 try:
@@ -21,4 +22,4 @@ try:
 except Exception as e:
     print('%-28s FAILED %s' % ('$name', e))
 "
-done | tee -a gpurun_out/sweep.log
+done | tee -a "$OUT/sweep.log"
