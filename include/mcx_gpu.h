@@ -318,6 +318,33 @@ int mcx_graph_add_records(mcx_graph *g, const void *recs, uint64_t nrecs, int fi
  * db_graph_intersect_edges, src/graph/db_graph.c:630-673).  *removed = k-mers dropped. */
 int mcx_graph_intersect_finish(mcx_graph *g, uint64_t *removed);
 
+/* `clean` (src/commands/ctx_clean.c, src/tools/clean_graph.c) in two calls, so that the host can pick
+ * the threshold from the "before" histogram in between.  Both flush pending inserts first and refuse
+ * (MCX_ERR_ARG) a graph split over devices or in intersect mode, and graphs of 2^31 k-mers or more.
+ * mcx_graph_unitig_stats splits the graph into unitigs (db_unitig.c: maximal chains over the union of
+ *   the colours' edges, each k-mer in exactly one) on the device and keeps the decomposition for
+ *   mcx_graph_clean.  before (NULL: not wanted) = 3 x MCX_CLEAN_NBINS counts: k-mer coverage (summed
+ *   over colours, saturating), unitig median coverage, unitig length, each clipped to the last bin.
+ *   Scratch: MCX_CLEAN_BYTES_PER_KMER per k-mer + MCX_CLEAN_BYTES_PER_SLOT per table slot + the radix
+ *   sort's temporary, held until mcx_graph_clean; MCX_ERR_NOMEM when the free HBM cannot hold it.
+ * mcx_graph_clean removes every unitig whose median coverage is < covg_threshold or that is a tip
+ *   (length < min_keep_tip and indeg(first) + outdeg(last) <= 1); 0 switches that test off.  Kept
+ *   k-mers lose, in every colour, the edges to removed (or absent) k-mers; removed k-mers leave the
+ *   table.  The decisions are made once, on the graph as mcx_graph_unitig_stats saw it (which runs
+ *   first if it has not, or if the k-mer count has changed since).  after = the same three histograms
+ *   over the kept unitigs. */
+#define MCX_CLEAN_NBINS 1000
+#define MCX_CLEAN_BYTES_PER_KMER 64
+#define MCX_CLEAN_BYTES_PER_SLOT 4
+typedef struct {
+  uint64_t num_tips, num_tip_kmers;                            /* UnitigCleanerStats, clean_graph.c */
+  uint64_t num_low_covg_unitigs, num_low_covg_unitig_kmers;
+  uint64_t num_tip_and_low_unitigs, num_tip_and_low_unitig_kmers;
+  uint64_t nkmers_before, nkmers_removed;
+} mcx_clean_stats;
+int mcx_graph_unitig_stats(mcx_graph *g, uint64_t *before);
+int mcx_graph_clean(mcx_graph *g, uint32_t covg_threshold, uint32_t min_keep_tip, mcx_clean_stats *stats, uint64_t *after);
+
 /* `inferedges`: infer_kmer_edges (src/tools/infer_edges.c) for every record of `recs` (.ctx body
  * layout, ncols == the graph's colours) against the k-mers loaded into the graph.  Each edge that some
  * colour lacks (default, --all) or that some colour has and another lacks (MCX_INFER_POP, --pop)

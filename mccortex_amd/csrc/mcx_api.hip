@@ -29,6 +29,7 @@
 #include "mcx_streamfc.h"
 #include "mcx_ubench.h"
 #include "mcx_infer.h"
+#include "mcx_clean.h"
 
 using namespace mcx;
 
@@ -264,6 +265,7 @@ struct mcx_graph {
   mcx_group *as_group = nullptr;
   uint32_t own_lbo = 0;  // > 0: a shard of a group that deals the keys out by minimizer (exchange format v3): log2 shards
   unsigned long long *d_infer = nullptr;  // inferedges: [records modified, lookups] of the current call
+  struct CleanCache *clean = nullptr;     // clean: the unitig decomposition of mcx_graph_unitig_stats (mcx_clean.h)
 };
 
 // how the kernels that walk records / reads on every shard tell their own keys (mcx_kernels.h: OwnerSpec)
@@ -461,6 +463,8 @@ extern "C" int mcx_graph_create_shard(mcx_graph **out, int kmer_size, int ncols,
   return MCX_OK;
 }
 
+static void clean_drop(mcx_graph *g);
+
 extern "C" void mcx_graph_destroy(mcx_graph *g)
 {
   if (g && g->as_group) { group_destroy(g->as_group); delete g; return; }
@@ -487,6 +491,7 @@ extern "C" void mcx_graph_destroy(mcx_graph *g)
   if (g->d_ctr) (void)hipFree(g->d_ctr);
   if (g->d_readstrt) (void)hipFree(g->d_readstrt);
   if (g->d_infer) (void)hipFree(g->d_infer);
+  clean_drop(g);
   if (g->h_ctr) (void)hipHostFree(g->h_ctr);
   if (g->h_full) (void)hipHostFree(g->h_full);
   if (g->h_snap) {
@@ -506,6 +511,7 @@ extern "C" int mcx_graph_reset(mcx_graph *g)
   }
   if (!g) return fail(MCX_ERR_ARG, "null graph");
   HIP_TRY(hipSetDevice(g->device));
+  clean_drop(g);
   HIP_TRY(hipMemsetAsync(g->t.rec, 0, g->table_bytes, g->stream));
   HIP_TRY(hipMemsetAsync(touch_base(g), 0, kTouchHdr + g->touch_bytes, g->stream));
   HIP_TRY(hipMemsetAsync(g->d_ctr, 0, sizeof(Counters), g->stream));
@@ -3118,6 +3124,234 @@ extern "C" int mcx_graph_infer_edges(mcx_graph *g, void *recs, uint64_t nrecs, i
     return rc;
   }
   return infer_end(g, nmodified);
+}
+
+// ---------------------------------------------------------------------------
+// clean (ctx_clean.c, clean_graph.c): unitigs, median coverage, tips, prune -- mcx_clean.h
+// ---------------------------------------------------------------------------
+// What mcx_graph_unitig_stats leaves for mcx_graph_clean: per k-mer its slot, union edges, summed coverage
+// and unitig id; per unitig id its length, median and end degrees; map: slot -> dense id.
+struct CleanCache {
+  uint64_t n = 0, checksum = 0;  // the table it describes: k-mer count and k_checksum (keys, coverage, edges)
+  DevBuf<uint64_t> slot_of;
+  DevBuf<uint32_t> map, cov, uid, len, med;
+  DevBuf<uint8_t> ue, ends;
+};
+
+static void clean_drop(mcx_graph *g)
+{
+  delete g->clean;
+  g->clean = nullptr;
+}
+
+// the refusals and the closing flush; *n = k-mers in the table
+static int clean_begin(mcx_graph *g, uint64_t *n)
+{
+  if (!g) return fail(MCX_ERR_ARG, "null graph");
+  if (g->as_group || g->group || g->t.lbo || g->own_lbo)
+    return fail(MCX_ERR_ARG, "clean needs the whole table on one device, not a graph split over devices (unitigs cross shards)");
+  if (g->hidden >= 0) return fail(MCX_ERR_ARG, "clean does not take a graph in intersect mode");
+  HIP_TRY(hipSetDevice(g->device));
+  int rc = fetch_counters(g);
+  if (rc != MCX_OK) return rc;
+  *n = g->h_ctr->novel;
+  if (*n >= (1ull << 31)) return fail(MCX_ERR_ARG, "clean takes graphs of fewer than 2^31 k-mers (%llu)", (unsigned long long)*n);
+  return MCX_OK;
+}
+
+static unsigned cl_grid(const mcx_graph *g, uint64_t items)
+{
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, (uint64_t)g->grid));
+}
+
+static uint32_t cl_sort_end_bit(uint64_t n) { return 32u + (uint32_t)std::max(1, 64 - __builtin_clzll(std::max<uint64_t>(n, 1))); }
+
+template <int W> static int unitig_stats_t(mcx_graph *g, uint64_t n, uint64_t *before)
+{
+  hipStream_t st = g->stream;
+  clean_drop(g);
+  CleanCache *c = new CleanCache;
+  g->clean = c;
+  c->n = n;
+  const uint64_t n2 = 2 * n, nn = std::max<uint64_t>(n, 1);
+  // the whole footprint up front, so that a graph too large fails here with a clear message
+  size_t sort_tmp = 0;
+  HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_tmp, (uint64_t *)nullptr, (uint64_t *)nullptr, nn, 0, cl_sort_end_bit(n), st));
+  {
+    size_t f = 0, tot = 0;
+    HIP_TRY(hipMemGetInfo(&f, &tot));
+    const uint64_t need = nn * (uint64_t)MCX_CLEAN_BYTES_PER_KMER + g->t.nslots * (uint64_t)MCX_CLEAN_BYTES_PER_SLOT + sort_tmp;
+    if (need > f)
+      return fail(MCX_ERR_NOMEM, "clean needs %.1f GB of device scratch for %llu k-mers, %.1f GB are free", need / 1e9,
+                  (unsigned long long)n, f / 1e9);
+  }
+  HIP_TRY(c->slot_of.alloc(nn));
+  HIP_TRY(c->map.alloc(std::max<uint64_t>(g->t.nslots, 1)));
+  HIP_TRY(c->cov.alloc(nn));
+  HIP_TRY(c->uid.alloc(nn));
+  HIP_TRY(c->len.alloc(nn));
+  HIP_TRY(c->med.alloc(nn));
+  HIP_TRY(c->ue.alloc(nn));
+  HIP_TRY(c->ends.alloc(nn));
+  DevBuf<unsigned long long> d_cur, d_hist;
+  DevBuf<uint32_t> nxt[2], mn[2], d_changed;
+  DevBuf<uint8_t> lk;
+  HIP_TRY(d_cur.alloc(1));
+  HIP_TRY(d_hist.alloc(3 * kClBins));
+  HIP_TRY(hipMemsetAsync(d_cur, 0, 8, st));
+  HIP_TRY(hipMemsetAsync(d_hist, 0, 3 * kClBins * 8, st));
+  {
+    SpanGuard sp(g, "k_cl_compact");
+    hipLaunchKernelGGL(k_cl_compact, dim3(cl_grid(g, g->t.nslots)), dim3(256), 0, st, g->t, (uint32_t)g->ncols, nn, c->slot_of.p,
+                       c->map.p, c->ue.p, c->cov.p, d_cur.p);
+  }
+  HIP_TRY(hipGetLastError());
+  unsigned long long found = 0;
+  HIP_TRY(hipMemcpyAsync(&found, d_cur, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (found != n) return fail(MCX_ERR_HIP, "table scan found %llu k-mers, counter says %llu", found, (unsigned long long)n);
+  if (n) {
+    // A. links, B. ranking
+    for (int b = 0; b < 2; b++) { HIP_TRY(nxt[b].alloc(n2)); HIP_TRY(mn[b].alloc(n2)); }
+    HIP_TRY(lk.alloc(n));
+    HIP_TRY(d_changed.alloc(1));
+    {
+      SpanGuard sp(g, "k_cl_links");
+      LAUNCH_W4(g->W, k_cl_links, dim3(cl_grid(g, n)), dim3(256), 0, st, g->t, g->k, n, c->slot_of.p, c->map.p, c->ue.p, lk.p,
+                nxt[0].p, mn[0].p);
+    }
+    HIP_TRY(hipGetLastError());
+    int cur = 0;
+    for (int round = 0;; round++) {
+      if (round > 40) return fail(MCX_ERR_HIP, "unitig ranking did not settle");  // 2^40 steps exceed any chain of < 2^31 k-mers
+      uint32_t changed = 0;
+      HIP_TRY(hipMemsetAsync(d_changed, 0, 4, st));
+      {
+        SpanGuard sp(g, "k_cl_jump");
+        hipLaunchKernelGGL(k_cl_jump, dim3(cl_grid(g, n2)), dim3(256), 0, st, n2, lk.p, nxt[cur].p, mn[cur].p, nxt[cur ^ 1].p,
+                           mn[cur ^ 1].p, d_changed.p);
+      }
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      cur ^= 1;
+      if (!changed) break;
+    }
+    HIP_TRY(hipMemsetAsync(c->len, 0, n * 4, st));
+    {
+      SpanGuard sp(g, "k_cl_unitig");
+      hipLaunchKernelGGL(k_cl_unitig, dim3(cl_grid(g, n)), dim3(256), 0, st, n, nxt[cur].p, mn[cur].p, lk.p, c->ue.p, c->uid.p,
+                         c->len.p, c->ends.p);
+    }
+    HIP_TRY(hipGetLastError());
+    // C. medians: sorting (unitig id << 32 | coverage) puts each unitig's coverages together, in order.  The two
+    // nxt arrays (8 n bytes each) hold the keys now.
+    uint64_t *keys = reinterpret_cast<uint64_t *>(nxt[0].p), *sorted = reinterpret_cast<uint64_t *>(nxt[1].p);
+    {
+      SpanGuard sp(g, "k_cl_keys");
+      hipLaunchKernelGGL(k_cl_keys, dim3(cl_grid(g, n)), dim3(256), 0, st, n, c->uid.p, c->cov.p, keys);
+    }
+    HIP_TRY(hipGetLastError());
+    DevBuf<uint8_t> tmp;
+    HIP_TRY(tmp.alloc(std::max<size_t>(sort_tmp, 1)));
+    {
+      SpanGuard sp(g, "radix_sort_keys");
+      HIP_TRY(rocprim::radix_sort_keys((void *)tmp.p, sort_tmp, keys, sorted, n, 0, cl_sort_end_bit(n), st));
+    }
+    {
+      SpanGuard sp(g, "k_cl_median");
+      hipLaunchKernelGGL(k_cl_median, dim3(cl_grid(g, n)), dim3(256), 0, st, n, (const uint64_t *)sorted, c->len.p, c->med.p,
+                         d_hist.p + kClBins);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+      SpanGuard sp(g, "k_cl_kmer_hist");
+      hipLaunchKernelGGL(k_cl_kmer_hist, dim3(cl_grid(g, n)), dim3(256), 0, st, n, c->cov.p, c->uid.p, (const uint8_t *)nullptr,
+                         d_hist.p);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));  // before the scratch is freed
+  }
+  if (before) HIP_TRY(hipMemcpyAsync(before, d_hist, 3 * kClBins * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_unitig_stats(mcx_graph *g, uint64_t *before)
+{
+  uint64_t n = 0, cs = 0;
+  int rc = clean_begin(g, &n);
+  if (rc == MCX_OK) rc = mcx_graph_checksum(g, &cs, nullptr);
+  if (rc != MCX_OK) return rc;
+  switch (g->W) {
+    case 1: rc = unitig_stats_t<1>(g, n, before); break;
+    case 2: rc = unitig_stats_t<2>(g, n, before); break;
+    case 3: rc = unitig_stats_t<3>(g, n, before); break;
+    default: rc = unitig_stats_t<4>(g, n, before); break;
+  }
+  if (rc != MCX_OK) { (void)hipStreamSynchronize(g->stream); clean_drop(g); }
+  else g->clean->checksum = cs;
+  return rc;
+}
+
+extern "C" int mcx_graph_clean(mcx_graph *g, uint32_t covg_threshold, uint32_t min_keep_tip, mcx_clean_stats *stats, uint64_t *after)
+{
+  uint64_t n = 0;
+  int rc = clean_begin(g, &n);
+  if (rc != MCX_OK) return rc;
+  // The decomposition is used only if it describes the table as it is now: any insert, record load, inferedges or
+  // intersect since then changes the count or the checksum over keys, coverage and edges, and the passes run again.
+  uint64_t cs = 0;
+  rc = mcx_graph_checksum(g, &cs, nullptr);
+  if (rc == MCX_OK && (!g->clean || g->clean->n != n || g->clean->checksum != cs)) rc = mcx_graph_unitig_stats(g, nullptr);
+  if (rc != MCX_OK) return rc;
+  CleanCache *c = g->clean;
+  hipStream_t st = g->stream;
+  DevBuf<unsigned long long> d_st, d_hist;
+  DevBuf<uint8_t> keep;
+  HIP_TRY(d_st.alloc(8));
+  HIP_TRY(d_hist.alloc(3 * kClBins));
+  HIP_TRY(keep.alloc(std::max<uint64_t>(n, 1)));
+  HIP_TRY(hipMemsetAsync(d_st, 0, 8 * 8, st));
+  HIP_TRY(hipMemsetAsync(d_hist, 0, 3 * kClBins * 8, st));
+  if (n) {
+    {
+      SpanGuard sp(g, "k_cl_decide");
+      hipLaunchKernelGGL(k_cl_decide, dim3(cl_grid(g, n)), dim3(256), 0, st, n, c->len.p, c->med.p, c->ends.p, covg_threshold,
+                         min_keep_tip, keep.p, d_st.p, d_hist.p + kClBins);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+      SpanGuard sp(g, "k_cl_kmer_hist");
+      hipLaunchKernelGGL(k_cl_kmer_hist, dim3(cl_grid(g, n)), dim3(256), 0, st, n, c->cov.p, c->uid.p, (const uint8_t *)keep.p,
+                         d_hist.p);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+      SpanGuard sp(g, "k_cl_prune_edges");
+      LAUNCH_W4(g->W, k_cl_prune_edges, dim3(cl_grid(g, n)), dim3(256), 0, st, g->t, g->k, (uint32_t)g->ncols, n, c->slot_of.p,
+                c->map.p, c->ue.p, c->uid.p, keep.p);
+    }
+    HIP_TRY(hipGetLastError());
+    {
+      SpanGuard sp(g, "k_cl_tombstone");
+      hipLaunchKernelGGL(k_cl_tombstone, dim3(cl_grid(g, n)), dim3(256), 0, st, g->t, n, c->slot_of.p, c->uid.p, keep.p, g->d_ctr,
+                         d_st.p + 6);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  unsigned long long h[8];
+  HIP_TRY(hipMemcpyAsync(h, d_st, sizeof(h), hipMemcpyDeviceToHost, st));
+  if (after) HIP_TRY(hipMemcpyAsync(after, d_hist, 3 * kClBins * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  clean_drop(g);  // the decomposition described the graph before the prune
+  if (stats) {
+    stats->num_tips = h[0]; stats->num_tip_kmers = h[1];
+    stats->num_low_covg_unitigs = h[2]; stats->num_low_covg_unitig_kmers = h[3];
+    stats->num_tip_and_low_unitigs = h[4]; stats->num_tip_and_low_unitig_kmers = h[5];
+    stats->nkmers_before = n; stats->nkmers_removed = h[6];
+  }
+  return MCX_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -21,7 +21,7 @@ SYMBOLS = [
     "mcx_graph_nkmers", "mcx_graph_device_stats", "mcx_graph_stream", "mcx_graph_export",
     "mcx_kmer_from_str", "mcx_kmer_canonical", "mcx_kmer_hash", "mcx_pack_bases", "mcx_pack_reads_host", "mcx_pack_stream_dev", "mcx_graph_add_packed_dev",
     "mcx_ubench_stream", "mcx_ubench_random_rmw", "mcx_graph_insert_stats", "mcx_multi_exchange_bytes", "mcx_graph_hashtest", "mcx_hashtest_func", "mcx_debug_probe",
-    "mcx_graph_infer_edges", "mcx_graph_infer_edges_dev",
+    "mcx_graph_infer_edges", "mcx_graph_infer_edges_dev", "mcx_graph_unitig_stats", "mcx_graph_clean",
 ]
 
 
@@ -54,6 +54,17 @@ class RecordStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class CleanStats(C.Structure):
+    """mcx_clean_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("num_tips", "num_tip_kmers", "num_low_covg_unitigs", "num_low_covg_unitig_kmers",
+                                          "num_tip_and_low_unitigs", "num_tip_and_low_unitig_kmers", "nkmers_before",
+                                          "nkmers_removed")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+CLEAN_NBINS = 1000
 RECORDS_MUST_EXIST = 1
 INFER_POP, INFER_PRESENCE_COVG = 1, 2
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -94,6 +105,8 @@ def lib():
     L.mcx_sort_records.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_int]
     L.mcx_records_sorted.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
     L.mcx_graph_intersect_finish.argtypes = [vp, u64p]
+    L.mcx_graph_unitig_stats.argtypes = [vp, vp]
+    L.mcx_graph_clean.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(CleanStats), vp]
     L.mcx_graph_infer_edges.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, u64p]
     L.mcx_graph_infer_edges_dev.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, u64p]
     L.mcx_superk_supported.argtypes = [C.c_int]
@@ -333,6 +346,25 @@ class Graph:
         _check(self.L.mcx_graph_infer_edges_dev(self.h, _ptr(d_recs), int(nrecs), self.ncols, self._infer_flags(pop, presence),
                                                 C.byref(n)))
         return int(n.value)
+
+    @staticmethod
+    def _clean_hists(a):
+        return {"kmer_covg": a[:CLEAN_NBINS], "unitig_covg": a[CLEAN_NBINS:2 * CLEAN_NBINS], "unitig_len": a[2 * CLEAN_NBINS:]}
+
+    def unitig_stats(self):
+        """`clean`'s first pass: split the graph into unitigs on the device and return the "before" histograms
+        {kmer_covg, unitig_covg (median), unitig_len}, 1000 bins each; the decomposition is kept for clean()"""
+        a = np.zeros(3 * CLEAN_NBINS, dtype=np.uint64)
+        _check(self.L.mcx_graph_unitig_stats(self.h, _ptr(a)))
+        return self._clean_hists(a)
+
+    def clean(self, threshold, tips):
+        """remove unitigs with median coverage < threshold and tips shorter than `tips` k-mers (0 = off):
+        returns (stats dict, "after" histograms of the kept unitigs)"""
+        a = np.zeros(3 * CLEAN_NBINS, dtype=np.uint64)
+        st = CleanStats()
+        _check(self.L.mcx_graph_clean(self.h, int(threshold), int(tips), C.byref(st), _ptr(a)))
+        return st.as_dict(), self._clean_hists(a)
 
     def kmer_covg(self):
         """per colour: (k-mers with coverage, summed coverage) -- db_graph_get_kmer_covg"""

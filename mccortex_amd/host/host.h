@@ -129,11 +129,17 @@ bool ctx_reader_from_direct(const ctx_reader *r); /* file_filter_from_direct: no
 size_t ctx_write_header_raw(FILE *fh, const ctx_reader *r);
 void ctx_reader_close(ctx_reader *r);
 
+/* cleaning_pick_kmer_threshold (src/tools/clean_graph.c): the unitig cleaning threshold from the k-mer coverage
+ * histogram (arrlen bins), or -1; the outputs may be NULL (clean_thresh.c) */
+int cleaning_pick_kmer_threshold(const uint64_t *kmer_covg, size_t arrlen, double *alpha_est, double *beta_est,
+                                 double *false_pos, double *false_neg);
+
 /* ---- commands ---- */
 int ctx_build(int argc, char **argv);
 int ctx_sort(int argc, char **argv);
 int ctx_index(int argc, char **argv);
 int ctx_infer_edges(int argc, char **argv); /* src/commands/ctx_infer_edges.c */
+int ctx_clean(int argc, char **argv);       /* src/commands/ctx_clean.c */
 int ctx_hashtest(int argc, char **argv); /* src/commands/ctx_exp_hashtest.c */
 
 #endif
