@@ -479,6 +479,41 @@ void *mcx_graph_stream(mcx_graph *g);
 typedef int (*mcx_sink_fn)(void *ctx, const void *records, size_t nbytes);
 int mcx_graph_export(mcx_graph *g, int sorted, mcx_sink_fn sink, void *ctx);
 
+/* `unitigs` (src/commands/ctx_unitigs.c): every unitig of the decomposition above as text, written by kernels
+ * and handed to `sink` in consecutive byte ranges (like mcx_graph_export's).  The decomposition of
+ * mcx_graph_unitig_stats is reused when it still describes the table, and made otherwise.  Coverage is not
+ * used; edges are the union over the colours.  The same refusals as `clean`; the table is only read.
+ * The text depends on the graph alone (not on the table's size or load, the "grid" knob or the chunk size):
+ *   - every unitig is normalised in all three formats: a chain starts at the end with the lower key, a closed
+ *     cycle at its lowest key read forwards, a single k-mer is forward;
+ *   - unitigs are numbered 0, 1, ... in ascending order of the key of their first k-mer, and appear so;
+ *   - FASTA: ">unitig<i> prev=<P> next=<N>\n<seq>\n".  GFA: "H\tVN:Z:1.0", the S lines, then the L lines.
+ *     DOT: three preamble lines, the node lines, a blank line, the edge lines, "}";
+ *   - an L / DOT edge line is printed for an edge that leaves a unitig end when the key of that end k-mer is
+ *     below the key of the neighbour k-mer, or when the two are the same k-mer and not both sides are reverse
+ *     (_print_edge with `node < next` decided by key); the lines are sorted by (source unitig, left end
+ *     before right end, edge base ACGT).
+ * Scratch while the call runs, beside the decomposition: MCX_UNITIGS_BYTES_PER_KMER per k-mer and
+ * MCX_UNITIGS_BYTES_PER_UNITIG per unitig (GFA / DOT; FASTA needs 104 less), plus the radix sort's temporary.
+ * mcx_graph_configure(g, "unitigs_chunk", bytes) caps the chunk (tests of the chunk seams).
+ * mcx_graph_unitigs_dev writes no text: it fills caller-allocated device arrays (NULL: not wanted), the
+ * per-k-mer ones in dense order with nkmers entries -- keys (W words each, most significant first), unitig
+ * number, rank in the normalised unitig, orientation there (1 = reverse complement) -- and the per-unitig ones
+ * by unitig number (at most nkmers entries): index of the first k-mer in the per-k-mer arrays, length. */
+enum { MCX_UNITIGS_FASTA = 0, MCX_UNITIGS_GFA = 1, MCX_UNITIGS_DOT = 2 };
+enum { MCX_UNITIGS_POINTS = 1 }; /* DOT: print unitigs as points (-P) */
+#define MCX_UNITIGS_BYTES_PER_KMER 65
+#define MCX_UNITIGS_BYTES_PER_UNITIG 170
+typedef struct { uint64_t num_unitigs, num_kmers, num_bytes, num_cycles; } mcx_unitigs_stats;
+typedef struct {
+  uint64_t *keys;
+  uint32_t *unitig, *rank;
+  uint8_t *orient;
+  uint32_t *first, *length;
+} mcx_unitigs_arrays;
+int mcx_graph_unitigs(mcx_graph *g, int format, uint32_t flags, mcx_sink_fn sink, void *ctx, mcx_unitigs_stats *stats);
+int mcx_graph_unitigs_dev(mcx_graph *g, const mcx_unitigs_arrays *out, mcx_unitigs_stats *stats);
+
 /* Host-side primitives exported for parity tests of rows A-C (no device). */
 void mcx_kmer_from_str(const char *seq, int kmer_size, uint64_t *words_out);
 void mcx_kmer_canonical(const uint64_t *words_in, int kmer_size, uint64_t *key_out, int *orient_out);

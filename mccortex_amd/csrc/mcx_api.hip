@@ -30,6 +30,7 @@
 #include "mcx_ubench.h"
 #include "mcx_infer.h"
 #include "mcx_clean.h"
+#include "mcx_unitigs.h"
 
 using namespace mcx;
 
@@ -184,6 +185,7 @@ struct mcx_graph {
   uint64_t stage_alloc = 0;
   int cur = 0;
   int grid = 0;
+  uint64_t unitigs_chunk = 0;            // test knob: bytes per chunk of mcx_graph_unitigs (0 = the staging buffers' size)
   int grid_stream = 0, grid_split = 0, grid_insert = 0;  // 0 = default; blocks of the three build kernels (experiments with concurrent launches)
   // ---- deferred (partition -> LDS insert) path, mcx_defer.h ----
   bool defer = true;
@@ -1388,6 +1390,7 @@ extern "C" int mcx_graph_configure(mcx_graph *g, const char *key, uint64_t value
     g->grid = value ? (int)value : cus * 8;  // (launches only: nothing is allocated per block of g->grid)
     return MCX_OK;
   }
+  if (!strcmp(key, "unitigs_chunk")) { g->unitigs_chunk = value; return MCX_OK; }  // test knob: chunk seams anywhere in the text
   if (!strcmp(key, "grid_stream")) { g->grid_stream = (int)value; return MCX_OK; }
   if (!strcmp(key, "grid_split")) { g->grid_split = (int)value; return MCX_OK; }
   if (!strcmp(key, "grid_insert")) { g->grid_insert = (int)value; return MCX_OK; }
@@ -3353,6 +3356,278 @@ extern "C" int mcx_graph_clean(mcx_graph *g, uint32_t covg_threshold, uint32_t m
   }
   return MCX_OK;
 }
+
+// ---------------------------------------------------------------------------
+// unitigs (ctx_unitigs.c): rank, order, emit -- mcx_unitigs.h
+// ---------------------------------------------------------------------------
+// what the rank and order passes leave for the emit (or for mcx_graph_unitigs_dev)
+struct UnWork {
+  uint64_t n = 0, nu = 0, ncycles = 0, unit_bytes = 0, edge_bytes = 0;
+  DevBuf<uint32_t> kun, krk, ufirst, ulast, ulen, ubase, etgt;
+  DevBuf<uint8_t> kori, upn, bases;
+  DevBuf<uint64_t> uoff, eoff;
+};
+
+static void un_clock(const char *what, double &t0)
+{
+  static const bool on = getenv("MCX_TIMING") != nullptr;
+  if (!on) return;
+  const double t = now_s();
+  fprintf(stderr, "[timing]   unitigs %8.1f ms  %s\n", (t - t0) * 1e3, what);
+  t0 = t;
+}
+
+template <class In> static int un_scan(mcx_graph *g, const In *in, uint64_t *out, uint64_t cnt)
+{
+  size_t tmp_bytes = 0;
+  HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, in, out, (uint64_t)0, cnt, rocprim::plus<uint64_t>(), g->stream));
+  DevBuf<uint8_t> tmp;
+  HIP_TRY(tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+  HIP_TRY(rocprim::exclusive_scan((void *)tmp.p, tmp_bytes, in, out, (uint64_t)0, cnt, rocprim::plus<uint64_t>(), g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));  // before tmp goes
+  return MCX_OK;
+}
+
+#define UN_LAUNCH(NAME, ITEMS, ...)                                                              \
+  do {                                                                                           \
+    SpanGuard sp_(g, #NAME);                                                                     \
+    hipLaunchKernelGGL(NAME, dim3(cl_grid(g, ITEMS)), dim3(256), 0, st, __VA_ARGS__);            \
+    HIP_TRY(hipGetLastError());                                                                  \
+  } while (0)
+#define UN_LAUNCH_W(NAME, ITEMS, ...)                                                            \
+  do {                                                                                           \
+    SpanGuard sp_(g, #NAME);                                                                     \
+    LAUNCH_W4(g->W, NAME, dim3(cl_grid(g, ITEMS)), dim3(256), 0, st, __VA_ARGS__);               \
+    HIP_TRY(hipGetLastError());                                                                  \
+  } while (0)
+
+// pointer jumping until a round finishes no node
+static int un_jump(mcx_graph *g, uint64_t m, const uint32_t *list, const uint8_t *lk, uint64_t *pk, uint32_t *d_changed)
+{
+  hipStream_t st = g->stream;
+  for (int round = 0;; round++) {
+    if (round > 40) return fail(MCX_ERR_HIP, "unitig ranking did not settle");  // (rounds halve the distance left: 31 suffice)
+    uint32_t changed = 0;
+    HIP_TRY(hipMemsetAsync(d_changed, 0, 4, st));
+    UN_LAUNCH(k_un_jump, m, m, list, lk, pk, d_changed);
+    HIP_TRY(hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!changed) return MCX_OK;
+  }
+}
+
+// A. rank and B. order; fmt < 0: no text is wanted (no record lengths beyond FASTA's, no edge lines)
+static int unitigs_prepare(mcx_graph *g, int fmt, UnWork &w)
+{
+  uint64_t n = 0, cs = 0;
+  int rc = clean_begin(g, &n);
+  if (rc == MCX_OK) rc = mcx_graph_checksum(g, &cs, nullptr);
+  // the decomposition is reused when it describes the table as it is now (the test mcx_graph_clean makes)
+  if (rc == MCX_OK && (!g->clean || g->clean->n != n || g->clean->checksum != cs)) rc = mcx_graph_unitig_stats(g, nullptr);
+  if (rc != MCX_OK) return rc;
+  w.n = n;
+  if (!n) return MCX_OK;
+  const CleanCache *c = g->clean;
+  hipStream_t st = g->stream;
+  const uint64_t n2 = 2 * n;
+  const int tfmt = fmt < 0 ? kUnFasta : fmt;
+  double t0 = now_s();
+  DevBuf<uint32_t> nxt0, list, d_changed, head, unum;
+  DevBuf<uint64_t> pk, starts, sorted, ks, ks2;
+  DevBuf<uint8_t> lk;
+  DevBuf<unsigned long long> d_cnt, mk;
+  HIP_TRY(nxt0.alloc(n2));
+  HIP_TRY(list.alloc(n2));  // k_cl_links' window minima first (not used here), then the nodes of closed cycles
+  HIP_TRY(pk.alloc(n2));
+  HIP_TRY(lk.alloc(n));
+  HIP_TRY(d_changed.alloc(1));
+  HIP_TRY(d_cnt.alloc(4));
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, 4 * 8, st));
+  UN_LAUNCH_W(k_cl_links, n, g->t, g->k, n, c->slot_of.p, c->map.p, c->ue.p, lk.p, nxt0.p, list.p);
+  UN_LAUNCH(k_un_init, n2, n2, (const uint32_t *)nxt0.p, pk.p);
+  if ((rc = un_jump(g, n2, nullptr, lk, pk, d_changed)) != MCX_OK) return rc;
+  UN_LAUNCH(k_un_mark, n, n, lk.p, (const uint64_t *)pk.p, list.p, d_cnt.p);
+  unsigned long long h_cnt[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  un_clock("chains ranked", t0);
+  if (const uint64_t m = h_cnt[0]) {  // oriented nodes on closed cycles
+    HIP_TRY(mk.alloc(n));
+    for (uint32_t wd = 0; wd < (uint32_t)g->W; wd++) {
+      UN_LAUNCH(k_un_cyc_reset, m, m, (const uint32_t *)list.p, (const uint32_t *)c->uid.p, mk.p);
+      UN_LAUNCH(k_un_cyc_min, m, g->t, m, (const uint32_t *)list.p, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint8_t *)lk.p, wd, mk.p);
+      UN_LAUNCH(k_un_cyc_keep, m, g->t, m, (const uint32_t *)list.p, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, lk.p, wd, (const unsigned long long *)mk.p);
+    }
+    UN_LAUNCH(k_un_cut, m, m, (const uint32_t *)list.p, (const uint32_t *)nxt0.p, lk.p, d_cnt.p + 1);
+    UN_LAUNCH(k_un_reinit, m, m, (const uint32_t *)list.p, (const uint32_t *)nxt0.p, (const uint8_t *)lk.p, pk.p);
+    if ((rc = un_jump(g, m, list, lk, pk, d_changed)) != MCX_OK) return rc;
+    un_clock("cycles cut and ranked", t0);
+  }
+  // B. order
+  HIP_TRY(head.alloc(n));
+  HIP_TRY(starts.alloc(n));
+  HIP_TRY(hipMemsetAsync(head, 0, n * 4, st));  // (every unitig id gets its head below; a missing one must not point outside)
+  UN_LAUNCH_W(k_un_heads, n, g->t, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint64_t *)pk.p, head.p, starts.p, d_cnt.p + 2);
+  HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t nu = h_cnt[2];
+  w.nu = nu;
+  w.ncycles = h_cnt[1];
+  if (!nu || nu > n) return fail(MCX_ERR_HIP, "unitig ranking found %llu unitigs in %llu k-mers", (unsigned long long)nu, (unsigned long long)n);
+  HIP_TRY(sorted.alloc(nu));
+  HIP_TRY(ks.alloc(nu));
+  HIP_TRY(ks2.alloc(nu));
+  {
+    // LSD over the key words, least significant first, every pass stable (the sorted export's multi-word sort)
+    size_t tmp_bytes = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, nu, 0, 64, st));
+    DevBuf<uint8_t> tmp;
+    HIP_TRY(tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+    uint64_t *cur = starts.p, *nxt = sorted.p;
+    for (int wd = g->W - 1; wd >= 0; wd--) {
+      UN_LAUNCH(k_un_keyword, nu, g->t, nu, (const uint64_t *)c->slot_of.p, (const uint64_t *)cur, (uint32_t)wd, ks.p);
+      SpanGuard sp(g, "radix_sort_pairs");
+      HIP_TRY(rocprim::radix_sort_pairs((void *)tmp.p, tmp_bytes, ks.p, ks2.p, cur, nxt, nu, 0, wd ? 64 : 2 * g->k - 64 * (g->W - 1), st));
+      std::swap(cur, nxt);
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (cur != sorted.p) std::swap(starts.p, sorted.p);  // sorted = the permutation after the last pass
+  }
+  HIP_TRY(unum.alloc(n));
+  HIP_TRY(hipMemsetAsync(unum, 0, n * 4, st));
+  HIP_TRY(w.ufirst.alloc(nu));
+  HIP_TRY(w.ulast.alloc(nu));
+  HIP_TRY(w.ulen.alloc(nu));
+  HIP_TRY(w.upn.alloc(nu));
+  HIP_TRY(w.uoff.alloc(nu + 1));
+  HIP_TRY(w.ubase.alloc(nu + 1));
+  HIP_TRY(hipMemsetAsync(w.uoff.p + nu, 0, 8, st));
+  UN_LAUNCH(k_un_number, nu, nu, tfmt, g->k, (const uint64_t *)sorted.p, (const uint32_t *)c->uid.p, (const uint32_t *)c->len.p, (const uint32_t *)head.p,
+            (const uint64_t *)pk.p, (const uint8_t *)c->ue.p, unum.p, w.ufirst.p, w.ulast.p, w.ulen.p, w.upn.p, w.uoff.p);
+  if ((rc = un_scan(g, (const uint64_t *)w.uoff.p, w.uoff.p, nu + 1)) != MCX_OK) return rc;
+  {
+    // positions in the base array: fewer than 2^31 k-mers, so 32 bits hold them (scanned in 64, narrowed by ks)
+    DevBuf<uint64_t> b64;
+    HIP_TRY(b64.alloc(nu + 1));
+    if ((rc = un_scan(g, (const uint32_t *)w.ulen.p, b64.p, nu)) != MCX_OK) return rc;
+    UN_LAUNCH(k_un_narrow, nu, nu, (const uint64_t *)b64.p, w.ubase.p);
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  HIP_TRY(hipMemcpyAsync(&w.unit_bytes, w.uoff.p + nu, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(w.kun.alloc(n));
+  HIP_TRY(w.krk.alloc(n));
+  HIP_TRY(w.kori.alloc(n));
+  HIP_TRY(w.bases.alloc(n));
+  UN_LAUNCH_W(k_un_place, n, g->t, g->k, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint32_t *)head.p, (const uint32_t *)unum.p,
+              (const uint64_t *)pk.p, (const uint32_t *)w.ubase.p, w.kun.p, w.krk.p, w.kori.p, w.bases.p);
+  if (fmt == kUnGfa || fmt == kUnDot) {
+    DevBuf<uint8_t> elen;
+    HIP_TRY(w.etgt.alloc(8 * nu));
+    HIP_TRY(elen.alloc(8 * nu + 1));
+    HIP_TRY(w.eoff.alloc(8 * nu + 1));
+    HIP_TRY(hipMemsetAsync(elen.p + 8 * nu, 0, 1, st));
+    UN_LAUNCH_W(k_un_edges, 2 * nu, g->t, g->k, fmt, nu, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p, (const uint8_t *)c->ue.p,
+                (const uint32_t *)w.ufirst.p, (const uint32_t *)w.ulast.p, (const uint32_t *)w.kun.p, (const uint32_t *)w.krk.p,
+                (const uint8_t *)w.kori.p, w.etgt.p, elen.p);
+    if ((rc = un_scan(g, (const uint8_t *)elen.p, w.eoff.p, 8 * nu + 1)) != MCX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(&w.edge_bytes, w.eoff.p + 8 * nu, 8, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));  // before the scratch of this function goes
+  un_clock("ordered and placed", t0);
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_unitigs(mcx_graph *g, int format, uint32_t flags, mcx_sink_fn sink, void *ctx, mcx_unitigs_stats *stats)
+{
+  if (!g || !sink) return fail(MCX_ERR_ARG, "null argument");
+  if (format != MCX_UNITIGS_FASTA && format != MCX_UNITIGS_GFA && format != MCX_UNITIGS_DOT) return fail(MCX_ERR_ARG, "unknown unitigs format %d", format);
+  if (flags & ~(uint32_t)MCX_UNITIGS_POINTS) return fail(MCX_ERR_ARG, "unknown unitigs flags 0x%x", flags);
+  if ((flags & MCX_UNITIGS_POINTS) && format != MCX_UNITIGS_DOT) return fail(MCX_ERR_ARG, "MCX_UNITIGS_POINTS is for MCX_UNITIGS_DOT only");
+  UnWork w;
+  int rc = unitigs_prepare(g, format, w);
+  if (rc == MCX_OK) rc = ensure_stage(g);
+  if (rc != MCX_OK) return rc;
+  hipStream_t st = g->stream;
+  HIP_TRY(hipStreamSynchronize(st));  // the staging buffers are ours now
+  HIP_TRY(hipStreamSynchronize(g->cstream));
+  // the text: pre | unitig records | mid | edge lines | post
+  UnText lit;
+  memset(&lit, 0, sizeof(lit));
+  size_t pre = 0, mid = 0, post = 0;
+  if (format == MCX_UNITIGS_GFA) pre = (size_t)snprintf(lit.s, sizeof(lit.s), "H\tVN:Z:1.0\n");
+  if (format == MCX_UNITIGS_DOT) {
+    pre = (size_t)snprintf(lit.s, sizeof(lit.s), "digraph G {\n  edge [dir=both arrowhead=none arrowtail=none color=\"blue\"]\n  node [%s, fontname=courier, fontsize=9]\n",
+                           (flags & MCX_UNITIGS_POINTS) ? "shape=point, label=none" : "shape=none");
+    mid = (size_t)snprintf(lit.s + pre, sizeof(lit.s) - pre, "\n");
+    post = (size_t)snprintf(lit.s + pre + mid, sizeof(lit.s) - pre - mid, "}\n");
+  }
+  // section s covers text bytes [sec[s], sec[s + 1])
+  const uint64_t sec[6] = {0, pre, pre + w.unit_bytes, pre + w.unit_bytes + mid, pre + w.unit_bytes + mid + w.edge_bytes,
+                           pre + w.unit_bytes + mid + w.edge_bytes + post};
+  const uint64_t total = sec[5];
+  uint64_t chunk = std::min<uint64_t>(kStageBytes, g->stage_alloc) & ~15ull;
+  if (g->unitigs_chunk) chunk = std::min<uint64_t>(chunk, g->unitigs_chunk);
+  UnUnits uu{g->t, g->k, format, g->W, w.nu, w.n, w.uoff.p, g->clean ? g->clean->slot_of.p : nullptr, w.ufirst.p, w.ubase.p, w.upn.p, w.bases.p};
+  UnEdges ue{g->k, format, 8 * w.nu, w.eoff.p, w.etgt.p};
+  auto produce = [&](uint64_t c0, int b) -> int {  // emit text bytes [c0, c0 + chunk) into buffer b, then copy them out
+    const uint64_t c1 = std::min(total, c0 + chunk);
+    for (int s = 0; s < 5; s++) {
+      const uint64_t lo = std::max(c0, sec[s]), hi = std::min(c1, sec[s + 1]);
+      if (lo >= hi) continue;
+      uint8_t *dst = (uint8_t *)g->d_stage[b];
+      if (s == 1) UN_LAUNCH(k_un_emit<UnUnits>, (hi - lo + 15) / 16 + 1, uu, lo - sec[1], hi - lo, dst, lo - c0);
+      else if (s == 3) UN_LAUNCH(k_un_emit<UnEdges>, (hi - lo + 15) / 16 + 1, ue, lo - sec[3], hi - lo, dst, lo - c0);
+      else {
+        const uint64_t from = (s == 0 ? 0 : s == 2 ? pre : pre + mid) + (lo - sec[s]);
+        hipLaunchKernelGGL(k_un_text, dim3(1), dim3(64), 0, st, lit, from, hi - lo, dst + (lo - c0));
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    HIP_TRY(hipEventRecord(g->ev[b], st));
+    HIP_TRY(hipStreamWaitEvent(g->cstream, g->ev[b], 0));
+    HIP_TRY(hipMemcpyAsync(g->h_stage[b], g->d_stage[b], c1 - c0, hipMemcpyDeviceToHost, g->cstream));
+    HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
+    return MCX_OK;
+  };
+  // chunk i + 1 is emitted while chunk i is copied out and handed to the sink; a buffer is emitted into again only
+  // after the sink has returned from it
+  double t0 = now_s();
+  if (total) rc = produce(0, 0);
+  int b = 0;
+  for (uint64_t c0 = 0; c0 < total && rc == MCX_OK; c0 += chunk, b ^= 1) {
+    if (c0 + chunk < total && (rc = produce(c0 + chunk, b ^ 1)) != MCX_OK) break;
+    HIP_TRY(hipEventSynchronize(g->ev_copy[b]));
+    if (sink(ctx, g->h_stage[b], (size_t)(std::min(total, c0 + chunk) - c0)) != 0) rc = fail(MCX_ERR_SINK, "unitigs sink failed");
+  }
+  (void)hipStreamSynchronize(st);  // leave nothing in flight on the staging buffers
+  (void)hipStreamSynchronize(g->cstream);
+  un_clock("text emitted and delivered", t0);
+  if (rc != MCX_OK) return rc;
+  if (stats) { stats->num_unitigs = w.nu; stats->num_kmers = w.n; stats->num_bytes = total; stats->num_cycles = w.ncycles; }
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_unitigs_dev(mcx_graph *g, const mcx_unitigs_arrays *out, mcx_unitigs_stats *stats)
+{
+  if (!g || !out) return fail(MCX_ERR_ARG, "null argument");
+  UnWork w;
+  int rc = unitigs_prepare(g, -1, w);
+  if (rc != MCX_OK) return rc;
+  hipStream_t st = g->stream;
+  if (w.n) {
+    if (out->keys) UN_LAUNCH_W(k_un_keys, w.n, g->t, w.n, (const uint64_t *)g->clean->slot_of.p, out->keys);
+    if (out->unitig) HIP_TRY(hipMemcpyAsync(out->unitig, w.kun, w.n * 4, hipMemcpyDeviceToDevice, st));
+    if (out->rank) HIP_TRY(hipMemcpyAsync(out->rank, w.krk, w.n * 4, hipMemcpyDeviceToDevice, st));
+    if (out->orient) HIP_TRY(hipMemcpyAsync(out->orient, w.kori, w.n, hipMemcpyDeviceToDevice, st));
+    if (out->first) UN_LAUNCH(k_un_first, w.nu, w.nu, (const uint32_t *)w.ufirst.p, out->first);
+    if (out->length) HIP_TRY(hipMemcpyAsync(out->length, w.ulen, w.nu * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  if (stats) { stats->num_unitigs = w.nu; stats->num_kmers = w.n; stats->num_bytes = 0; stats->num_cycles = w.ncycles; }
+  return MCX_OK;
+}
+#undef UN_LAUNCH
+#undef UN_LAUNCH_W
 
 // ---------------------------------------------------------------------------
 // export

@@ -22,6 +22,7 @@ SYMBOLS = [
     "mcx_kmer_from_str", "mcx_kmer_canonical", "mcx_kmer_hash", "mcx_pack_bases", "mcx_pack_reads_host", "mcx_pack_stream_dev", "mcx_graph_add_packed_dev",
     "mcx_ubench_stream", "mcx_ubench_random_rmw", "mcx_graph_insert_stats", "mcx_multi_exchange_bytes", "mcx_graph_hashtest", "mcx_hashtest_func", "mcx_debug_probe",
     "mcx_graph_infer_edges", "mcx_graph_infer_edges_dev", "mcx_graph_unitig_stats", "mcx_graph_clean",
+    "mcx_graph_unitigs", "mcx_graph_unitigs_dev",
 ]
 
 
@@ -64,7 +65,22 @@ class CleanStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class UnitigsStats(C.Structure):
+    """mcx_unitigs_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("num_unitigs", "num_kmers", "num_bytes", "num_cycles")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class UnitigsArrays(C.Structure):
+    """mcx_unitigs_arrays (device pointers)"""
+    _fields_ = [(n, C.c_void_p) for n in ("keys", "unitig", "rank", "orient", "first", "length")]
+
+
 CLEAN_NBINS = 1000
+UNITIGS_FORMATS = {"fasta": 0, "gfa": 1, "dot": 2}
+UNITIGS_POINTS = 1
 RECORDS_MUST_EXIST = 1
 INFER_POP, INFER_PRESENCE_COVG = 1, 2
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -107,6 +123,8 @@ def lib():
     L.mcx_graph_intersect_finish.argtypes = [vp, u64p]
     L.mcx_graph_unitig_stats.argtypes = [vp, vp]
     L.mcx_graph_clean.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(CleanStats), vp]
+    L.mcx_graph_unitigs.argtypes = [vp, C.c_int, C.c_uint32, SINK_FN, vp, C.POINTER(UnitigsStats)]
+    L.mcx_graph_unitigs_dev.argtypes = [vp, C.POINTER(UnitigsArrays), C.POINTER(UnitigsStats)]
     L.mcx_graph_infer_edges.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, u64p]
     L.mcx_graph_infer_edges_dev.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, u64p]
     L.mcx_superk_supported.argtypes = [C.c_int]
@@ -221,6 +239,7 @@ class Graph:
         self.L = lib()
         self.k, self.ncols, self.W = kmer_size, ncols, _words(kmer_size)
         self.nparts, self.part = nparts, part
+        self.device = device if devices is None else devices[0]
         h = C.c_void_p()
         if devices is not None:
             arr = (C.c_int * len(devices))(*devices)
@@ -440,6 +459,46 @@ class Graph:
     @property
     def stream(self):
         return self.L.mcx_graph_stream(self.h)
+
+    def unitigs_chunks(self, format="fasta", points=False, stats=None):
+        """`unitigs`: yields the text in consecutive chunks (the whole text is produced on the first step; `stats`,
+        a dict, receives num_unitigs, num_kmers, num_bytes, num_cycles)"""
+        if format not in UNITIGS_FORMATS:
+            raise ValueError("unitigs format: one of %s" % ", ".join(sorted(UNITIGS_FORMATS)))
+        parts = []
+
+        def sink(_ctx, ptr, n):
+            parts.append(C.string_at(ptr, n))
+            return 0
+
+        st = UnitigsStats()
+        _check(self.L.mcx_graph_unitigs(self.h, UNITIGS_FORMATS[format], UNITIGS_POINTS if points else 0, SINK_FN(sink), None,
+                                        C.byref(st)))
+        if stats is not None:
+            stats.update(st.as_dict())
+        yield from parts
+
+    def unitigs(self, format="fasta", points=False, stats=None):
+        """`unitigs` (ctx_unitigs.c): every unitig of the graph as FASTA, GFA or DOT text, written on the device;
+        normalised, numbered by the key of the first k-mer (include/mcx_gpu.h states the contract)"""
+        return b"".join(self.unitigs_chunks(format, points, stats))
+
+    def unitigs_dev(self):
+        """mcx_graph_unitigs_dev into torch tensors on the graph's device: (dict of keys[n,W] (int64 bit patterns),
+        unitig[n], rank[n], orient[n], first[u], length[u], stats dict)"""
+        import torch
+        n = max(self.nkmers, 1)
+        dev = "cuda:%d" % self.device
+        t = {"keys": torch.zeros((n, self.W), dtype=torch.int64, device=dev), "unitig": torch.zeros(n, dtype=torch.int32, device=dev),
+             "rank": torch.zeros(n, dtype=torch.int32, device=dev), "orient": torch.zeros(n, dtype=torch.uint8, device=dev),
+             "first": torch.zeros(n, dtype=torch.int32, device=dev), "length": torch.zeros(n, dtype=torch.int32, device=dev)}
+        arr = UnitigsArrays(*[t[name].data_ptr() for name, _ in UnitigsArrays._fields_])
+        st = UnitigsStats()
+        torch.cuda.synchronize(self.device)
+        _check(self.L.mcx_graph_unitigs_dev(self.h, C.byref(arr), C.byref(st)))
+        nk, nu = int(st.num_kmers), int(st.num_unitigs)
+        out = {name: (v[:nu] if name in ("first", "length") else v[:nk]) for name, v in t.items()}
+        return out, st.as_dict()
 
     def export(self, sorted_=True):
         """Records in .ctx body layout as one bytes object."""

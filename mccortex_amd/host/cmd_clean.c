@@ -123,7 +123,7 @@ static void write_len_hist(const char *path, const uint64_t *hist, size_t len, s
 }
 
 /* graph_load (graphs_load.c:86-214): the file's colours through its filter into the table */
-static void load_file(mcx_graph *g, ctx_reader *r)
+void ctx_load_graph_file(mcx_graph *g, ctx_reader *r)
 {
   char a[64], b[64];
   status("[GReader] %s kmers, %s filesize", ulong_to_str((uint64_t)(r->num_kmers < 0 ? 0 : r->num_kmers), a),
@@ -298,7 +298,7 @@ int ctx_clean(int argc, char **argv)
   for (size_t i = 0; i < ncols; i++) col_info_init(&cols[i]);
   for (size_t i = 0; i < nfiles; i++)
     for (size_t j = 0; j < gfiles[i].nfilter; j++) col_info_merge(&cols[gfiles[i].filter[j].into], &gfiles[i].ginfo[gfiles[i].filter[j].from]);
-  for (size_t i = 0; i < nfiles; i++) load_file(g, &gfiles[i]);
+  for (size_t i = 0; i < nfiles; i++) ctx_load_graph_file(g, &gfiles[i]);
 
   uint64_t initial_nkmers = 0;
   check(mcx_graph_nkmers(g, &initial_nkmers), "nkmers");

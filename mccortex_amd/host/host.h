@@ -140,6 +140,10 @@ int ctx_sort(int argc, char **argv);
 int ctx_index(int argc, char **argv);
 int ctx_infer_edges(int argc, char **argv); /* src/commands/ctx_infer_edges.c */
 int ctx_clean(int argc, char **argv);       /* src/commands/ctx_clean.c */
+int ctx_unitigs(int argc, char **argv);     /* src/commands/ctx_unitigs.c */
+/* graph_load: one opened file's colours through its filter into the device table (cmd_clean.c) */
+struct mcx_graph;
+void ctx_load_graph_file(struct mcx_graph *g, ctx_reader *r);
 int ctx_hashtest(int argc, char **argv); /* src/commands/ctx_exp_hashtest.c */
 
 #endif
