@@ -326,7 +326,10 @@ int mcx_graph_intersect_finish(mcx_graph *g, uint64_t *removed);
  *   mcx_graph_clean.  before (NULL: not wanted) = 3 x MCX_CLEAN_NBINS counts: k-mer coverage (summed
  *   over colours, saturating), unitig median coverage, unitig length, each clipped to the last bin.
  *   Scratch: MCX_CLEAN_BYTES_PER_KMER per k-mer + MCX_CLEAN_BYTES_PER_SLOT per table slot + the radix
- *   sort's temporary, held until mcx_graph_clean; MCX_ERR_NOMEM when the free HBM cannot hold it.
+ *   sort's temporary while the call runs; MCX_ERR_NOMEM when the free HBM cannot hold it.  Kept on the handle
+ *   until the next prune (mcx_graph_clean, mcx_graph_pop_bubbles) or the next call that finds it stale: 27 bytes
+ *   per k-mer (slot, coverage, unitig id, length, median, union edges, end degrees, and the link bits that
+ *   mcx_graph_pop_bubbles finds the unitig ends with) + MCX_CLEAN_BYTES_PER_SLOT per slot.
  * mcx_graph_clean removes every unitig whose median coverage is < covg_threshold or that is a tip
  *   (length < min_keep_tip and indeg(first) + outdeg(last) <= 1); 0 switches that test off.  Kept
  *   k-mers lose, in every colour, the edges to removed (or absent) k-mers; removed k-mers leave the
@@ -344,6 +347,41 @@ typedef struct {
 } mcx_clean_stats;
 int mcx_graph_unitig_stats(mcx_graph *g, uint64_t *before);
 int mcx_graph_clean(mcx_graph *g, uint32_t covg_threshold, uint32_t min_keep_tip, mcx_clean_stats *stats, uint64_t *after);
+
+/* `popbubbles` (src/commands/ctx_pop_bubbles.c; pop_bubbles, mark_remove_bubbles, get_parallel_nodes and
+ * process_bubble of src/tools/pop_bubbles.c; prune_nodes_lacking_flag of src/graph/prune_nodes.c) on the
+ * decomposition of mcx_graph_unitig_stats, which is reused when it still describes the table and made
+ * otherwise.  All colours count as one: edges are their union, coverage is db_node_sum_covg.  Two unitigs are
+ * parallel when, one node out and one node back over every other edge, a start of one is found at each end of
+ * the other; of such a pair the branch with the lower mean coverage (sum / length, rounded down) loses, on
+ * equal means the alternative.  The loser goes if its mean is <= max_covg and its length <= max_klen (each
+ * ignored when <= 0) and the lengths differ by <= max_kdiff (ignored when < 0).  Kept k-mers lose, in every
+ * colour, the edges to removed k-mers; removed k-mers leave the table.
+ * The reference's result depends on the order in which its threads reach the unitigs (a losing alternative is
+ * marked visited and never takes its own turn).  Here the result is that of pop_bubbles() on one thread when
+ * every unitig is taken in its normal form (db_unitig_normalise: the end with the lower key first, a single
+ * k-mer forward) and the unitigs take their turn in ascending order of E(U), the smaller of the keys of U's two
+ * end k-mers: a function of the graph alone, not of the table's size or load or the "grid" knob.
+ * The same refusals as `clean` (MCX_ERR_ARG).  One more: when a unitig has siblings at both ends and one of its
+ * left siblings lies inside a unitig -- only one-sided edges allow that -- the call is refused (MCX_ERR_ARG; the
+ * table is left as it was), because the reference would walk a fragment of that unitig as the branch.  This is
+ * decided at the sibling, before it is known whether the fragment would end at a right sibling, so it also
+ * refuses graphs on which the sequential rule finds no bubble there.  `inferedges` makes the edges two-sided.
+ * Scratch beside the decomposition: MCX_POP_BYTES_PER_KMER per k-mer and MCX_POP_BYTES_PER_PAIR per parallel
+ * pair found (at most MCX_POP_BYTES_PER_UNITIG per unitig, far fewer in practice).  The pairs are counted by a
+ * first pass and the list has exactly that size; MCX_ERR_NOMEM when the free HBM cannot hold it. */
+#define MCX_POP_BYTES_PER_KMER 20
+#define MCX_POP_BYTES_PER_PAIR 8
+#define MCX_POP_BYTES_PER_UNITIG (16 * MCX_POP_BYTES_PER_PAIR)
+typedef struct {
+  uint64_t num_popped;        /* bubbles popped */
+  uint64_t num_pairs;         /* parallel pairs examined */
+  uint64_t nkmers_before;
+  uint64_t nkmers_removed;
+  uint64_t num_unitigs_removed;
+  uint32_t rounds;            /* rounds of the order resolution */
+} mcx_pop_stats;
+int mcx_graph_pop_bubbles(mcx_graph *g, int32_t max_covg, int32_t max_klen, int32_t max_kdiff, mcx_pop_stats *stats);
 
 /* `inferedges`: infer_kmer_edges (src/tools/infer_edges.c) for every record of `recs` (.ctx body
  * layout, ncols == the graph's colours) against the k-mers loaded into the graph.  Each edge that some

@@ -31,6 +31,7 @@
 #include "mcx_infer.h"
 #include "mcx_clean.h"
 #include "mcx_unitigs.h"
+#include "mcx_pop.h"
 
 using namespace mcx;
 
@@ -3133,12 +3134,13 @@ extern "C" int mcx_graph_infer_edges(mcx_graph *g, void *recs, uint64_t nrecs, i
 // clean (ctx_clean.c, clean_graph.c): unitigs, median coverage, tips, prune -- mcx_clean.h
 // ---------------------------------------------------------------------------
 // What mcx_graph_unitig_stats leaves for mcx_graph_clean: per k-mer its slot, union edges, summed coverage
-// and unitig id; per unitig id its length, median and end degrees; map: slot -> dense id.
+// and unitig id; per unitig id its length, median and end degrees; map: slot -> dense id; lk: the link bits of
+// k_cl_links (mcx_graph_pop_bubbles finds the unitig ends with them).
 struct CleanCache {
   uint64_t n = 0, checksum = 0;  // the table it describes: k-mer count and k_checksum (keys, coverage, edges)
   DevBuf<uint64_t> slot_of;
   DevBuf<uint32_t> map, cov, uid, len, med;
-  DevBuf<uint8_t> ue, ends;
+  DevBuf<uint8_t> ue, ends, lk;
 };
 
 static void clean_drop(mcx_graph *g)
@@ -3147,18 +3149,18 @@ static void clean_drop(mcx_graph *g)
   g->clean = nullptr;
 }
 
-// the refusals and the closing flush; *n = k-mers in the table
-static int clean_begin(mcx_graph *g, uint64_t *n)
+// the refusals and the closing flush; *n = k-mers in the table; `what` names the command in the messages
+static int clean_begin(mcx_graph *g, uint64_t *n, const char *what = "clean")
 {
   if (!g) return fail(MCX_ERR_ARG, "null graph");
   if (g->as_group || g->group || g->t.lbo || g->own_lbo)
-    return fail(MCX_ERR_ARG, "clean needs the whole table on one device, not a graph split over devices (unitigs cross shards)");
-  if (g->hidden >= 0) return fail(MCX_ERR_ARG, "clean does not take a graph in intersect mode");
+    return fail(MCX_ERR_ARG, "%s needs the whole table on one device, not a graph split over devices (unitigs cross shards)", what);
+  if (g->hidden >= 0) return fail(MCX_ERR_ARG, "%s does not take a graph in intersect mode", what);
   HIP_TRY(hipSetDevice(g->device));
   int rc = fetch_counters(g);
   if (rc != MCX_OK) return rc;
   *n = g->h_ctr->novel;
-  if (*n >= (1ull << 31)) return fail(MCX_ERR_ARG, "clean takes graphs of fewer than 2^31 k-mers (%llu)", (unsigned long long)*n);
+  if (*n >= (1ull << 31)) return fail(MCX_ERR_ARG, "%s takes graphs of fewer than 2^31 k-mers (%llu)", what, (unsigned long long)*n);
   return MCX_OK;
 }
 
@@ -3198,7 +3200,6 @@ template <int W> static int unitig_stats_t(mcx_graph *g, uint64_t n, uint64_t *b
   HIP_TRY(c->ends.alloc(nn));
   DevBuf<unsigned long long> d_cur, d_hist;
   DevBuf<uint32_t> nxt[2], mn[2], d_changed;
-  DevBuf<uint8_t> lk;
   HIP_TRY(d_cur.alloc(1));
   HIP_TRY(d_hist.alloc(3 * kClBins));
   HIP_TRY(hipMemsetAsync(d_cur, 0, 8, st));
@@ -3216,11 +3217,11 @@ template <int W> static int unitig_stats_t(mcx_graph *g, uint64_t n, uint64_t *b
   if (n) {
     // A. links, B. ranking
     for (int b = 0; b < 2; b++) { HIP_TRY(nxt[b].alloc(n2)); HIP_TRY(mn[b].alloc(n2)); }
-    HIP_TRY(lk.alloc(n));
+    HIP_TRY(c->lk.alloc(n));
     HIP_TRY(d_changed.alloc(1));
     {
       SpanGuard sp(g, "k_cl_links");
-      LAUNCH_W4(g->W, k_cl_links, dim3(cl_grid(g, n)), dim3(256), 0, st, g->t, g->k, n, c->slot_of.p, c->map.p, c->ue.p, lk.p,
+      LAUNCH_W4(g->W, k_cl_links, dim3(cl_grid(g, n)), dim3(256), 0, st, g->t, g->k, n, c->slot_of.p, c->map.p, c->ue.p, c->lk.p,
                 nxt[0].p, mn[0].p);
     }
     HIP_TRY(hipGetLastError());
@@ -3231,7 +3232,7 @@ template <int W> static int unitig_stats_t(mcx_graph *g, uint64_t n, uint64_t *b
       HIP_TRY(hipMemsetAsync(d_changed, 0, 4, st));
       {
         SpanGuard sp(g, "k_cl_jump");
-        hipLaunchKernelGGL(k_cl_jump, dim3(cl_grid(g, n2)), dim3(256), 0, st, n2, lk.p, nxt[cur].p, mn[cur].p, nxt[cur ^ 1].p,
+        hipLaunchKernelGGL(k_cl_jump, dim3(cl_grid(g, n2)), dim3(256), 0, st, n2, c->lk.p, nxt[cur].p, mn[cur].p, nxt[cur ^ 1].p,
                            mn[cur ^ 1].p, d_changed.p);
       }
       HIP_TRY(hipGetLastError());
@@ -3243,7 +3244,7 @@ template <int W> static int unitig_stats_t(mcx_graph *g, uint64_t n, uint64_t *b
     HIP_TRY(hipMemsetAsync(c->len, 0, n * 4, st));
     {
       SpanGuard sp(g, "k_cl_unitig");
-      hipLaunchKernelGGL(k_cl_unitig, dim3(cl_grid(g, n)), dim3(256), 0, st, n, nxt[cur].p, mn[cur].p, lk.p, c->ue.p, c->uid.p,
+      hipLaunchKernelGGL(k_cl_unitig, dim3(cl_grid(g, n)), dim3(256), 0, st, n, nxt[cur].p, mn[cur].p, c->lk.p, c->ue.p, c->uid.p,
                          c->len.p, c->ends.p);
     }
     HIP_TRY(hipGetLastError());
@@ -3354,6 +3355,148 @@ extern "C" int mcx_graph_clean(mcx_graph *g, uint32_t covg_threshold, uint32_t m
     stats->num_tip_and_low_unitigs = h[4]; stats->num_tip_and_low_unitig_kmers = h[5];
     stats->nkmers_before = n; stats->nkmers_removed = h[6];
   }
+  return MCX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// popbubbles (ctx_pop_bubbles.c, pop_bubbles.c): sums and ends, pairs, turns, prune -- mcx_pop.h
+// ---------------------------------------------------------------------------
+#define POP_LAUNCH(NAME, ITEMS, ...)                                                             \
+  do {                                                                                           \
+    SpanGuard sp_(g, #NAME);                                                                     \
+    hipLaunchKernelGGL(NAME, dim3(cl_grid(g, ITEMS)), dim3(256), 0, st, __VA_ARGS__);            \
+    HIP_TRY(hipGetLastError());                                                                  \
+  } while (0)
+#define POP_LAUNCH_W(NAME, ITEMS, ...)                                                           \
+  do {                                                                                           \
+    SpanGuard sp_(g, #NAME);                                                                     \
+    LAUNCH_W4(g->W, NAME, dim3(cl_grid(g, ITEMS)), dim3(256), 0, st, __VA_ARGS__);               \
+    HIP_TRY(hipGetLastError());                                                                  \
+  } while (0)
+
+static void pop_clock(const char *what, double &t0)
+{
+  static const bool on = getenv("MCX_TIMING") != nullptr;
+  if (!on) return;
+  const double t = now_s();
+  fprintf(stderr, "[timing]   popbubbles %8.1f ms  %s\n", (t - t0) * 1e3, what);
+  t0 = t;
+}
+
+extern "C" int mcx_graph_pop_bubbles(mcx_graph *g, int32_t max_covg, int32_t max_klen, int32_t max_kdiff, mcx_pop_stats *stats)
+{
+  uint64_t n = 0, cs = 0;
+  int rc = clean_begin(g, &n, "popbubbles");
+  if (rc == MCX_OK) rc = mcx_graph_checksum(g, &cs, nullptr);
+  double t0 = now_s();
+  // the decomposition is reused when it describes the table as it is now (the test mcx_graph_clean makes)
+  if (rc == MCX_OK && (!g->clean || g->clean->n != n || g->clean->checksum != cs)) rc = mcx_graph_unitig_stats(g, nullptr);
+  if (rc != MCX_OK) return rc;
+  pop_clock("decomposition (reused when it is current)", t0);
+  mcx_pop_stats out;
+  memset(&out, 0, sizeof(out));
+  out.nkmers_before = n;
+  if (stats) *stats = out;
+  if (!n) return MCX_OK;
+  CleanCache *c = g->clean;
+  hipStream_t st = g->stream;
+  // scratch: MCX_POP_BYTES_PER_KMER per k-mer; the pair list is sized by a counting pass of k_pop_pairs
+  size_t fr = 0, tot = 0;
+  HIP_TRY(hipMemGetInfo(&fr, &tot));
+  const uint64_t fixed = n * (uint64_t)MCX_POP_BYTES_PER_KMER + (64u << 20);
+  if (fixed > fr)
+    return fail(MCX_ERR_NOMEM, "popbubbles needs %.1f GB of device scratch for %llu k-mers, %.1f GB are free", fixed / 1e9,
+                (unsigned long long)n, fr / 1e9);
+  DevBuf<unsigned long long> sum, d_cnt;
+  DevBuf<uint32_t> ends, d_flag;
+  DevBuf<uint8_t> state, kill, wait, keep;
+  DevBuf<uint64_t> pairs;
+  HIP_TRY(sum.alloc(n));
+  HIP_TRY(ends.alloc(2 * n));
+  HIP_TRY(state.alloc(n));
+  HIP_TRY(kill.alloc(n));
+  HIP_TRY(wait.alloc(n));
+  HIP_TRY(keep.alloc(n));
+  HIP_TRY(d_cnt.alloc(4));  // pairs, popped, unitigs removed, k-mers removed
+  HIP_TRY(d_flag.alloc(2));  // a sibling inside a unitig; a round changed something
+  HIP_TRY(hipMemsetAsync(sum, 0, n * 8, st));
+  HIP_TRY(hipMemsetAsync(ends, 0xff, 2 * n * 4, st));
+  HIP_TRY(hipMemsetAsync(state, 0, n, st));
+  HIP_TRY(hipMemsetAsync(kill, 0, n, st));
+  HIP_TRY(hipMemsetAsync(wait, 0, n, st));
+  HIP_TRY(hipMemsetAsync(keep, 1, n, st));
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, 4 * 8, st));
+  HIP_TRY(hipMemsetAsync(d_flag, 0, 2 * 4, st));
+  // A. sums and ends
+  POP_LAUNCH(k_pop_sums, n, n, (const uint32_t *)c->uid.p, (const uint32_t *)c->cov.p, (const uint8_t *)c->lk.p, sum.p, ends.p);
+  POP_LAUNCH_W(k_pop_norm, n, g->t, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->len.p, ends.p);
+  if (getenv("MCX_TIMING")) HIP_TRY(hipStreamSynchronize(st));
+  pop_clock("sums and ends", t0);
+  // B. pairs: counted first (nothing is stored), then stored into a list of exactly that size
+  POP_LAUNCH_W(k_pop_pairs, n, g->t, g->k, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p, (const uint8_t *)c->ue.p,
+               (const uint32_t *)c->uid.p, (const uint32_t *)c->len.p, (const uint8_t *)c->lk.p, (const uint32_t *)ends.p, (uint64_t)0,
+               (uint64_t *)nullptr, d_cnt.p, d_flag.p);
+  unsigned long long np = 0;
+  uint32_t inside = 0;
+  HIP_TRY(hipMemcpyAsync(&np, d_cnt, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&inside, d_flag, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (inside)
+    return fail(MCX_ERR_ARG, "popbubbles: a sibling of a unitig end lies inside a unitig; the graph has one-sided edges there (run inferedges first)");
+  if (np) {
+    HIP_TRY(hipMemGetInfo(&fr, &tot));
+    if (np * (uint64_t)MCX_POP_BYTES_PER_PAIR + (64u << 20) > fr)
+      return fail(MCX_ERR_NOMEM, "popbubbles found %llu parallel pairs (%.1f GB), %.1f GB of HBM are free", np, np * 8 / 1e9, fr / 1e9);
+    HIP_TRY(pairs.alloc(np));
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, st));
+    POP_LAUNCH_W(k_pop_pairs, n, g->t, g->k, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p, (const uint8_t *)c->ue.p,
+                 (const uint32_t *)c->uid.p, (const uint32_t *)c->len.p, (const uint8_t *)c->lk.p, (const uint32_t *)ends.p, (uint64_t)np,
+                 pairs.p, d_cnt.p, d_flag.p);
+    unsigned long long np2 = 0;
+    HIP_TRY(hipMemcpyAsync(&np2, d_cnt, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (np2 != np) return fail(MCX_ERR_HIP, "the two passes over the parallel pairs disagree (%llu, %llu)", np, np2);
+  }
+  pop_clock("pairs", t0);
+  out.num_pairs = np;
+  unsigned long long h[4] = {np, 0, 0, 0};
+  if (np) {
+    POP_LAUNCH(k_pop_mark, np, np, pairs.p, (const unsigned long long *)sum.p, (const uint32_t *)c->len.p, max_covg, max_klen, max_kdiff);
+    // C. turns: a round decides every unitig whose possible removers are all decided; the relation leads from
+    // lower to higher E, so each round decides at least the undecided unitig with the lowest E
+    for (uint64_t round = 0;; round++) {
+      if (round > n + 1) return fail(MCX_ERR_HIP, "the order resolution did not settle");
+      uint32_t changed = 0;
+      HIP_TRY(hipMemsetAsync(d_flag.p + 1, 0, 4, st));
+      POP_LAUNCH(k_pop_threats, np, np, (const uint64_t *)pairs.p, (const uint8_t *)state.p, kill.p, wait.p);
+      POP_LAUNCH(k_pop_settle, n, n, (const uint32_t *)c->len.p, state.p, (const uint8_t *)kill.p, wait.p, d_flag.p + 1);
+      HIP_TRY(hipMemcpyAsync(&changed, d_flag.p + 1, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (!changed) break;
+      out.rounds++;
+    }
+    // D. losers
+    POP_LAUNCH(k_pop_apply, np, np, (const uint64_t *)pairs.p, (const unsigned long long *)sum.p, (const uint32_t *)c->len.p, max_covg,
+               max_klen, max_kdiff, (const uint8_t *)state.p, keep.p, d_cnt.p + 1);
+    POP_LAUNCH(k_pop_count, n, n, (const uint32_t *)c->len.p, (const uint8_t *)keep.p, d_cnt.p + 2);
+    HIP_TRY(hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    pop_clock("resolution", t0);
+  }
+  if (h[2]) {
+    POP_LAUNCH_W(k_cl_prune_edges, n, g->t, g->k, (uint32_t)g->ncols, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p,
+                 (const uint8_t *)c->ue.p, (const uint32_t *)c->uid.p, (const uint8_t *)keep.p);
+    POP_LAUNCH(k_cl_tombstone, n, g->t, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint8_t *)keep.p, g->d_ctr,
+               d_cnt.p + 3);
+    HIP_TRY(hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    clean_drop(g);  // the decomposition described the graph before the prune
+    pop_clock("prune", t0);
+  }
+  out.num_popped = h[1];
+  out.num_unitigs_removed = h[2];
+  out.nkmers_removed = h[3];
+  if (stats) *stats = out;
   return MCX_OK;
 }
 

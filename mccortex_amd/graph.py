@@ -22,7 +22,7 @@ SYMBOLS = [
     "mcx_kmer_from_str", "mcx_kmer_canonical", "mcx_kmer_hash", "mcx_pack_bases", "mcx_pack_reads_host", "mcx_pack_stream_dev", "mcx_graph_add_packed_dev",
     "mcx_ubench_stream", "mcx_ubench_random_rmw", "mcx_graph_insert_stats", "mcx_multi_exchange_bytes", "mcx_graph_hashtest", "mcx_hashtest_func", "mcx_debug_probe",
     "mcx_graph_infer_edges", "mcx_graph_infer_edges_dev", "mcx_graph_unitig_stats", "mcx_graph_clean",
-    "mcx_graph_unitigs", "mcx_graph_unitigs_dev",
+    "mcx_graph_unitigs", "mcx_graph_unitigs_dev", "mcx_graph_pop_bubbles",
 ]
 
 
@@ -60,6 +60,15 @@ class CleanStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("num_tips", "num_tip_kmers", "num_low_covg_unitigs", "num_low_covg_unitig_kmers",
                                           "num_tip_and_low_unitigs", "num_tip_and_low_unitig_kmers", "nkmers_before",
                                           "nkmers_removed")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class PopStats(C.Structure):
+    """mcx_pop_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("num_popped", "num_pairs", "nkmers_before", "nkmers_removed", "num_unitigs_removed")] + \
+               [("rounds", C.c_uint32)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -123,6 +132,7 @@ def lib():
     L.mcx_graph_intersect_finish.argtypes = [vp, u64p]
     L.mcx_graph_unitig_stats.argtypes = [vp, vp]
     L.mcx_graph_clean.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(CleanStats), vp]
+    L.mcx_graph_pop_bubbles.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PopStats)]
     L.mcx_graph_unitigs.argtypes = [vp, C.c_int, C.c_uint32, SINK_FN, vp, C.POINTER(UnitigsStats)]
     L.mcx_graph_unitigs_dev.argtypes = [vp, C.POINTER(UnitigsArrays), C.POINTER(UnitigsStats)]
     L.mcx_graph_infer_edges.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, u64p]
@@ -459,6 +469,14 @@ class Graph:
     @property
     def stream(self):
         return self.L.mcx_graph_stream(self.h)
+
+    def pop_bubbles(self, max_covg=-1, max_klen=-1, max_kdiff=-1):
+        """`popbubbles` (ctx_pop_bubbles.c): of two parallel unitigs the one with the lower mean coverage goes, if its mean
+        is <= max_covg and its length <= max_klen (<= 0: ignored) and the lengths differ by <= max_kdiff (< 0: ignored).
+        Returns the stats dict (num_popped, num_pairs, nkmers_before, nkmers_removed, num_unitigs_removed, rounds)"""
+        st = PopStats()
+        _check(self.L.mcx_graph_pop_bubbles(self.h, int(max_covg), int(max_klen), int(max_kdiff), C.byref(st)))
+        return st.as_dict()
 
     def unitigs_chunks(self, format="fasta", points=False, stats=None):
         """`unitigs`: yields the text in consecutive chunks (the whole text is produced on the first step; `stats`,
