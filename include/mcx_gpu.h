@@ -383,6 +383,54 @@ typedef struct {
 } mcx_pop_stats;
 int mcx_graph_pop_bubbles(mcx_graph *g, int32_t max_covg, int32_t max_klen, int32_t max_kdiff, mcx_pop_stats *stats);
 
+/* `subgraph` (src/commands/ctx_subgraph.c; subgraph_from_reads, mark_bkmer, mark_unitig, store_node_neighbours and
+ * extend of src/tools/subgraph.c; prune_nodes_lacking_flag of src/graph/prune_nodes.c): keep the k-mers within
+ * `dist` edges of the seed k-mers.  All colours count as one: the neighbours of a k-mer come from the union of the
+ * colours' edges, on both sides.  The result is a set -- a function of the graph, the seeds, dist and the flags
+ * alone, not of the table's size or load, the "grid" knob or the "subgraph_narrow" knob.
+ *   mcx_graph_subgraph_begin    flushes pending inserts and sets up the state on the handle: dense k-mer ids (the
+ *       decomposition of mcx_graph_unitig_stats when it still describes the table -- it is taken over and goes with
+ *       the state; otherwise a scan of the table), a mark bit per k-mer and one queue of as many 32-bit ids as there
+ *       are k-mers.  A k-mer enters the queue once, when its bit is set, so the queue cannot overflow: the
+ *       reference's "Please increase <mem> size" has no counterpart.  With MCX_SUBGRAPH_UNITIGS the decomposition
+ *       is made if it is not there.  The same refusals as `clean` (MCX_ERR_ARG): a graph split over devices or in
+ *       intersect mode, 2^31 k-mers or more.  Scratch: MCX_SUBGRAPH_BYTES_PER_KMER per k-mer, and where the ids
+ *       come from a scan MCX_SUBGRAPH_IDS_BYTES_PER_KMER per k-mer + MCX_CLEAN_BYTES_PER_SLOT per table slot;
+ *       MCX_ERR_NOMEM when the free HBM cannot hold it.  A second begin, mcx_graph_reset and mcx_graph_destroy
+ *       free the state.  The graph must not be modified between begin and finish: no inserts, and no
+ *       mcx_graph_clean or mcx_graph_pop_bubbles, which change edges the ids were made from without changing the k-mer
+ *       count that finish checks.
+ *   mcx_graph_subgraph_seed_reads / _seed_stream_dev    (READ_TO_BKMERS with no quality or homopolymer cutoff,
+ *       mark_bkmer / mark_unitig) may be called any number of times: every k-mer of the seeds that is in the graph
+ *       is marked; with MCX_SUBGRAPH_UNITIGS, its whole unitig (db_unitig_fetch).  Lower case counts as upper case,
+ *       any other byte ends a contig.  seed_reads takes the layout of mcx_graph_add_reads (read r is
+ *       bases[off[r] .. off[r + 1])) and goes through the pinned staging buffers as ASCII, in chunks bounded by what a
+ *       buffer holds (a read longer than a chunk goes in pieces); seed_stream_dev takes the layout
+ *       of mcx_graph_add_stream_dev (ASCII in HBM, 16-byte aligned, any non-base byte separates reads).
+ *   mcx_graph_subgraph_finish   extends the marked set by `dist` breadth-first levels (extend), complements it with
+ *       MCX_SUBGRAPH_INVERT, then prunes: unmarked k-mers leave the table, kept k-mers lose in every colour the
+ *       edges to removed k-mers -- and to k-mers that are not in the graph, which the extension passes over too
+ *       (the reference asserts).  Frees the state.  MCX_SUBGRAPH_UNITIGS must be given as it was to begin.
+ * A seed call or a finish without a begin returns MCX_ERR_ARG.
+ * The levels run on the device: a frontier of up to "subgraph_narrow" k-mers (mcx_graph_configure; maximum
+ * 256, default 0 = never, until the kernel has been timed against chained launches) is expanded by one workgroup that runs level after level in one launch; a larger one by
+ * one launch per level, 8 levels chained between two reads of the frontier size. */
+enum { MCX_SUBGRAPH_UNITIGS = 1, MCX_SUBGRAPH_INVERT = 2 };
+#define MCX_SUBGRAPH_BYTES_PER_KMER 6      /* queue 4, unitig flag 1, mark bit */
+#define MCX_SUBGRAPH_IDS_BYTES_PER_KMER 13 /* slot 8, summed coverage 4, union edges 1 */
+typedef struct {
+  uint64_t num_seed_kmers;   /* k-mer occurrences in the seeds (stats.num_kmers_loaded), in the graph or not */
+  uint64_t num_seed_found;   /* distinct k-mers marked before the extension (after the unitig grab) */
+  uint64_t nkmers_before, nkmers_kept, nkmers_removed;
+  uint32_t levels;           /* breadth-first levels that added k-mers */
+  uint32_t narrow_launches;  /* launches of the one-workgroup kernel */
+  uint64_t max_frontier;     /* largest frontier, the seeds' included */
+} mcx_subgraph_stats;
+int mcx_graph_subgraph_begin(mcx_graph *g, uint32_t flags);
+int mcx_graph_subgraph_seed_reads(mcx_graph *g, const uint8_t *bases, const uint64_t *read_offsets, uint64_t nreads);
+int mcx_graph_subgraph_seed_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes);
+int mcx_graph_subgraph_finish(mcx_graph *g, uint32_t dist, uint32_t flags, mcx_subgraph_stats *stats);
+
 /* `inferedges`: infer_kmer_edges (src/tools/infer_edges.c) for every record of `recs` (.ctx body
  * layout, ncols == the graph's colours) against the k-mers loaded into the graph.  Each edge that some
  * colour lacks (default, --all) or that some colour has and another lacks (MCX_INFER_POP, --pop)

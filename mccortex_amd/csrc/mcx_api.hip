@@ -32,6 +32,7 @@
 #include "mcx_clean.h"
 #include "mcx_unitigs.h"
 #include "mcx_pop.h"
+#include "mcx_subgraph.h"
 
 using namespace mcx;
 
@@ -269,6 +270,8 @@ struct mcx_graph {
   uint32_t own_lbo = 0;  // > 0: a shard of a group that deals the keys out by minimizer (exchange format v3): log2 shards
   unsigned long long *d_infer = nullptr;  // inferedges: [records modified, lookups] of the current call
   struct CleanCache *clean = nullptr;     // clean: the unitig decomposition of mcx_graph_unitig_stats (mcx_clean.h)
+  struct SubgraphState *subgraph = nullptr;  // subgraph: marks and queue between mcx_graph_subgraph_begin and _finish (mcx_subgraph.h)
+  uint32_t subgraph_narrow = 0;           // frontiers of up to this many k-mers go to k_sg_narrow (0: never; off until it is timed)
 };
 
 // how the kernels that walk records / reads on every shard tell their own keys (mcx_kernels.h: OwnerSpec)
@@ -467,6 +470,7 @@ extern "C" int mcx_graph_create_shard(mcx_graph **out, int kmer_size, int ncols,
 }
 
 static void clean_drop(mcx_graph *g);
+static void subgraph_drop(mcx_graph *g);
 
 extern "C" void mcx_graph_destroy(mcx_graph *g)
 {
@@ -495,6 +499,7 @@ extern "C" void mcx_graph_destroy(mcx_graph *g)
   if (g->d_readstrt) (void)hipFree(g->d_readstrt);
   if (g->d_infer) (void)hipFree(g->d_infer);
   clean_drop(g);
+  subgraph_drop(g);
   if (g->h_ctr) (void)hipHostFree(g->h_ctr);
   if (g->h_full) (void)hipHostFree(g->h_full);
   if (g->h_snap) {
@@ -515,6 +520,7 @@ extern "C" int mcx_graph_reset(mcx_graph *g)
   if (!g) return fail(MCX_ERR_ARG, "null graph");
   HIP_TRY(hipSetDevice(g->device));
   clean_drop(g);
+  subgraph_drop(g);
   HIP_TRY(hipMemsetAsync(g->t.rec, 0, g->table_bytes, g->stream));
   HIP_TRY(hipMemsetAsync(touch_base(g), 0, kTouchHdr + g->touch_bytes, g->stream));
   HIP_TRY(hipMemsetAsync(g->d_ctr, 0, sizeof(Counters), g->stream));
@@ -1392,6 +1398,7 @@ extern "C" int mcx_graph_configure(mcx_graph *g, const char *key, uint64_t value
     return MCX_OK;
   }
   if (!strcmp(key, "unitigs_chunk")) { g->unitigs_chunk = value; return MCX_OK; }  // test knob: chunk seams anywhere in the text
+  if (!strcmp(key, "subgraph_narrow")) { g->subgraph_narrow = (uint32_t)std::min<uint64_t>(value, (uint64_t)kSgBlock); return MCX_OK; }
   if (!strcmp(key, "grid_stream")) { g->grid_stream = (int)value; return MCX_OK; }
   if (!strcmp(key, "grid_split")) { g->grid_split = (int)value; return MCX_OK; }
   if (!strcmp(key, "grid_insert")) { g->grid_insert = (int)value; return MCX_OK; }
@@ -3498,6 +3505,268 @@ extern "C" int mcx_graph_pop_bubbles(mcx_graph *g, int32_t max_covg, int32_t max
   out.nkmers_removed = h[3];
   if (stats) *stats = out;
   return MCX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// subgraph (ctx_subgraph.c, subgraph.c): seeds, breadth-first extension, prune -- mcx_subgraph.h
+// ---------------------------------------------------------------------------
+// What lives between mcx_graph_subgraph_begin and mcx_graph_subgraph_finish.  The dense ids are the decomposition
+// of mcx_graph_unitig_stats when that is current (it moves here from the handle: the prune at the end outdates it
+// anyway), otherwise the output of k_cl_compact alone.
+struct SubgraphState {
+  uint64_t n = 0;
+  uint32_t flags = 0;
+  CleanCache *ids = nullptr;
+  DevBuf<uint32_t> mark, queue, ctl;
+  DevBuf<uint8_t> uflag;           // --unitigs: one flag per unitig id
+  DevBuf<unsigned long long> cnt;  // seed k-mer occurrences, k-mers marked by the seeds, k-mers removed
+  ~SubgraphState() { delete ids; }
+};
+
+static void subgraph_drop(mcx_graph *g)
+{
+  if (g->subgraph && g->stream) (void)hipStreamSynchronize(g->stream);
+  delete g->subgraph;
+  g->subgraph = nullptr;
+}
+
+static SgView sg_view(const SubgraphState *s)
+{
+  return SgView{s->ids->slot_of.p, s->ids->map.p, s->ids->ue.p, s->mark.p, s->queue.p, s->ctl.p, s->n};
+}
+
+constexpr uint32_t kSgLevelsPerRead = 8;  // wide levels chained on the stream between two reads of the frontier size
+
+extern "C" int mcx_graph_subgraph_begin(mcx_graph *g, uint32_t flags)
+{
+  uint64_t n = 0, cs = 0;
+  int rc = clean_begin(g, &n, "subgraph");
+  if (rc != MCX_OK) return rc;
+  if (flags & ~(uint32_t)(MCX_SUBGRAPH_UNITIGS | MCX_SUBGRAPH_INVERT)) return fail(MCX_ERR_ARG, "subgraph: unknown flags 0x%x", flags);
+  subgraph_drop(g);
+  rc = mcx_graph_checksum(g, &cs, nullptr);
+  if (rc != MCX_OK) return rc;
+  bool current = g->clean && g->clean->n == n && g->clean->checksum == cs;
+  if (!current && (flags & MCX_SUBGRAPH_UNITIGS)) {
+    if ((rc = mcx_graph_unitig_stats(g, nullptr)) != MCX_OK) return rc;
+    current = true;
+  }
+  const uint64_t nn = std::max<uint64_t>(n, 1), nslots = std::max<uint64_t>(g->t.nslots, 1);
+  {
+    size_t fr = 0, tot = 0;
+    HIP_TRY(hipMemGetInfo(&fr, &tot));
+    const uint64_t need = nn * (uint64_t)MCX_SUBGRAPH_BYTES_PER_KMER + (64u << 20) +
+                          (current ? 0 : nn * (uint64_t)MCX_SUBGRAPH_IDS_BYTES_PER_KMER + nslots * (uint64_t)MCX_CLEAN_BYTES_PER_SLOT);
+    if (need > fr)
+      return fail(MCX_ERR_NOMEM, "subgraph needs %.1f GB of device scratch for %llu k-mers, %.1f GB are free", need / 1e9,
+                  (unsigned long long)n, fr / 1e9);
+  }
+  SubgraphState *s = new SubgraphState;
+  g->subgraph = s;
+  s->n = n;
+  s->flags = flags;
+  hipStream_t st = g->stream;
+  auto build = [&]() -> int {
+    if (current) {
+      s->ids = g->clean;
+      g->clean = nullptr;
+    } else {
+      CleanCache *c = s->ids = new CleanCache;
+      c->n = n;
+      HIP_TRY(c->slot_of.alloc(nn));
+      HIP_TRY(c->map.alloc(nslots));
+      HIP_TRY(c->ue.alloc(nn));
+      HIP_TRY(c->cov.alloc(nn));
+      DevBuf<unsigned long long> d_cur;
+      HIP_TRY(d_cur.alloc(1));
+      HIP_TRY(hipMemsetAsync(d_cur, 0, 8, st));
+      {
+        SpanGuard sp(g, "k_cl_compact");
+        hipLaunchKernelGGL(k_cl_compact, dim3(cl_grid(g, g->t.nslots)), dim3(256), 0, st, g->t, (uint32_t)g->ncols, nn, c->slot_of.p,
+                           c->map.p, c->ue.p, c->cov.p, d_cur.p);
+      }
+      HIP_TRY(hipGetLastError());
+      unsigned long long found = 0;
+      HIP_TRY(hipMemcpyAsync(&found, d_cur, 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (found != n) return fail(MCX_ERR_HIP, "table scan found %llu k-mers, counter says %llu", found, (unsigned long long)n);
+    }
+    const uint64_t words = (nn + 31) / 32;
+    HIP_TRY(s->mark.alloc(words));
+    HIP_TRY(s->queue.alloc(nn));
+    HIP_TRY(s->ctl.alloc(kSgCtlWords));
+    HIP_TRY(s->cnt.alloc(3));
+    HIP_TRY(hipMemsetAsync(s->mark, 0, words * 4, st));
+    HIP_TRY(hipMemsetAsync(s->ctl, 0, kSgCtlWords * 4, st));
+    HIP_TRY(hipMemsetAsync(s->cnt, 0, 3 * 8, st));
+    if (flags & MCX_SUBGRAPH_UNITIGS) {
+      HIP_TRY(s->uflag.alloc(nn));
+      HIP_TRY(hipMemsetAsync(s->uflag, 0, nn, st));
+    }
+    return MCX_OK;
+  };
+  rc = build();
+  if (rc != MCX_OK) subgraph_drop(g);
+  return rc;
+}
+
+// the seed k-mers of one stream (L as submit_stream takes it), on the handle's stream
+static int subgraph_seed_launch(mcx_graph *g, const StreamLaunch &L)
+{
+  SubgraphState *s = g->subgraph;
+  const StreamArgs a = make_args(g, L);
+  const uint64_t nt = a.ntiles > a.tile0 ? a.ntiles - a.tile0 : 0;
+  if (!nt) return MCX_OK;
+  const bool un = (s->flags & MCX_SUBGRAPH_UNITIGS) != 0;
+  SpanGuard sp(g, "k_sg_seed");
+  LAUNCH_W4(g->W, k_sg_seed, dim3((unsigned)std::min<uint64_t>(nt, (uint64_t)g->grid)), dim3(kThreads), 0, g->stream, a, g->t, sg_view(s),
+            un ? (const uint32_t *)s->ids->uid.p : (const uint32_t *)nullptr, un ? s->uflag.p : (uint8_t *)nullptr, s->cnt.p);
+  HIP_TRY(hipGetLastError());
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_subgraph_seed_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes)
+{
+  if (!g) return fail(MCX_ERR_ARG, "null graph");
+  if (!g->subgraph) return fail(MCX_ERR_ARG, "subgraph: no mcx_graph_subgraph_begin before the seeds");
+  if (((uintptr_t)d_stream & 15) != 0) return fail(MCX_ERR_ARG, "stream must be 16-byte aligned");
+  if (!nbytes) return MCX_OK;
+  if (!d_stream) return fail(MCX_ERR_ARG, "null stream");
+  HIP_TRY(hipSetDevice(g->device));
+  StreamLaunch L{(const uint8_t *)d_stream, nbytes, 0, nbytes, nullptr};
+  return subgraph_seed_launch(g, L);
+}
+
+// Host seeds through the pinned staging buffers, in the chunk layout of the ASCII path of mcx_graph_add_reads: kCarry
+// positions carried over from the chunk before, then whole reads each followed by a separator (or a piece of a read
+// longer than a chunk); a chunk owns the k-mers that start kCarry - k positions in up to k before its end.
+extern "C" int mcx_graph_subgraph_seed_reads(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads)
+{
+  if (!g) return fail(MCX_ERR_ARG, "null graph");
+  if (!g->subgraph) return fail(MCX_ERR_ARG, "subgraph: no mcx_graph_subgraph_begin before the seeds");
+  if (nreads && (!bases || !off)) return fail(MCX_ERR_ARG, "null read buffers");
+  if (!nreads) return MCX_OK;
+  HIP_TRY(hipSetDevice(g->device));
+  int rc = ensure_stage(g);
+  if (rc != MCX_OK) return rc;
+  // new bytes per chunk: the staging buffers are sized for the packed layout of mcx_graph_add_reads by default, which is
+  // smaller than kCarry + kStageBytes + 64 ASCII bytes, so a chunk is bounded by what a buffer holds
+  const uint64_t cap = std::min<uint64_t>(kStageBytes, g->stage_alloc - kCarry - 64);
+  uint64_t r = 0, r_pos = 0;  // next read, bytes of it already staged
+  uint8_t carry[kCarry];
+  memset(carry, '\n', kCarry);
+  while (r < nreads) {
+    const int b = g->cur;
+    g->cur = (g->cur + 1) % mcx_graph::kStageBufs;
+    HIP_TRY(hipEventSynchronize(g->ev[b]));  // previous use of this buffer finished
+    uint8_t *hs = g->h_stage[b];
+    memcpy(hs, carry, kCarry);
+    uint64_t L = 0;
+    while (r < nreads) {
+      const uint64_t len = off[r + 1] - off[r], remain = len - r_pos;
+      if (r_pos == 0 && remain + 1 <= cap - L) {
+        memcpy(hs + kCarry + L, bases + off[r], len);
+        L += len;
+        hs[kCarry + L++] = '\n';
+        r++;
+      } else if (L == 0) {  // a read longer than a chunk (or its tail): a piece on its own
+        const uint64_t take = std::min(remain, cap - 1);
+        memcpy(hs + kCarry, bases + off[r] + r_pos, take);
+        L = take;
+        r_pos += take;
+        if (r_pos == len) { hs[kCarry + L++] = '\n'; r++; r_pos = 0; }
+        break;
+      } else {
+        break;
+      }
+    }
+    const uint64_t total = kCarry + L;
+    memcpy(carry, hs + total - kCarry, kCarry);
+    memset(hs + total, '\n', 64);  // the 16-byte chunk loads of the kernel stay inside the copy
+    HIP_TRY(hipMemcpyAsync(g->d_stage[b], hs, total + 64, hipMemcpyHostToDevice, g->stream));
+    StreamLaunch SL{g->d_stage[b], total, kCarry - (uint64_t)g->k, total - (uint64_t)g->k, nullptr};
+    rc = subgraph_seed_launch(g, SL);
+    HIP_TRY(hipEventRecord(g->ev[b], g->stream));
+    if (rc != MCX_OK) return rc;
+  }
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_subgraph_finish(mcx_graph *g, uint32_t dist, uint32_t flags, mcx_subgraph_stats *stats)
+{
+  if (!g) return fail(MCX_ERR_ARG, "null graph");
+  SubgraphState *s = g->subgraph;
+  if (!s) return fail(MCX_ERR_ARG, "subgraph: no mcx_graph_subgraph_begin before the finish");
+  if ((flags ^ s->flags) & MCX_SUBGRAPH_UNITIGS) return fail(MCX_ERR_ARG, "subgraph: the unitigs flag differs from the one given to begin");
+  if (flags & ~(uint32_t)(MCX_SUBGRAPH_UNITIGS | MCX_SUBGRAPH_INVERT)) return fail(MCX_ERR_ARG, "subgraph: unknown flags 0x%x", flags);
+  HIP_TRY(hipSetDevice(g->device));
+  int rc = fetch_counters(g);
+  if (rc != MCX_OK) return rc;
+  if (g->h_ctr->novel != s->n) {
+    subgraph_drop(g);
+    return fail(MCX_ERR_ARG, "subgraph: the graph changed between begin and finish");
+  }
+  hipStream_t st = g->stream;
+  const uint64_t n = s->n;
+  const SgView v = sg_view(s);
+  const uint32_t invert = (flags & MCX_SUBGRAPH_INVERT) ? 1u : 0u;
+  mcx_subgraph_stats out;
+  memset(&out, 0, sizeof(out));
+  uint32_t ctl[kSgCtlWords];
+  auto read_ctl = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(ctl, s->ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ctl[kSgOver]) return fail(MCX_ERR_HIP, "subgraph: the queue of %llu entries overflowed", (unsigned long long)n);
+    return MCX_OK;
+  };
+  auto run = [&]() -> int {
+    if (s->flags & MCX_SUBGRAPH_UNITIGS)
+      POP_LAUNCH(k_sg_grab, n, v, (const uint32_t *)s->ids->uid.p, (const uint8_t *)s->uflag.p, s->cnt.p);
+    hipLaunchKernelGGL(k_sg_open, dim3(1), dim3(1), 0, st, s->ctl.p);
+    HIP_TRY(hipGetLastError());
+    int rc2 = read_ctl();
+    if (rc2 != MCX_OK) return rc2;
+    // B. the extension: the frontier size read back picks the kernel
+    while (ctl[kSgLevel] < dist && ctl[kSgTail] != ctl[kSgHead]) {
+      const uint64_t f = ctl[kSgTail] - ctl[kSgHead];
+      if (g->subgraph_narrow && f <= g->subgraph_narrow) {
+        SpanGuard sp(g, "k_sg_narrow");
+        LAUNCH_W4(g->W, k_sg_narrow, dim3(1), dim3(kSgBlock), 0, st, g->t, g->k, v, dist, g->subgraph_narrow);
+        out.narrow_launches++;
+      } else {
+        // (a launch whose level is beyond dist or whose frontier is empty does nothing; the grids allow for a frontier
+        // that grows fourfold per level)
+        for (uint32_t j = 0; j < kSgLevelsPerRead; j++) {
+          SpanGuard sp(g, "k_sg_expand");
+          LAUNCH_W4(g->W, k_sg_expand, dim3(cl_grid(g, 8 * std::min<uint64_t>(n, f << std::min<uint32_t>(2 * j, 32)))), dim3(256), 0, st,
+                    g->t, g->k, v, dist);
+        }
+      }
+      HIP_TRY(hipGetLastError());
+      if ((rc2 = read_ctl()) != MCX_OK) return rc2;
+    }
+    // C. the prune
+    if (n) {
+      POP_LAUNCH_W(k_sg_prune_edges, n, g->t, g->k, (uint32_t)g->ncols, v, invert);
+      POP_LAUNCH(k_sg_tombstone, n, g->t, v, invert, g->d_ctr, s->cnt.p + 2);
+    }
+    unsigned long long h[3];
+    HIP_TRY(hipMemcpyAsync(h, s->cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out.num_seed_kmers = h[0];
+    out.num_seed_found = h[1];
+    out.nkmers_before = n;
+    out.nkmers_removed = h[2];
+    out.nkmers_kept = n - h[2];
+    out.levels = ctl[kSgAdded];
+    out.max_frontier = ctl[kSgMaxF];
+    return MCX_OK;
+  };
+  rc = run();
+  if (rc != MCX_OK) (void)hipStreamSynchronize(st);
+  subgraph_drop(g);  // (with the dense ids: they described the graph before the prune)
+  if (rc == MCX_OK && stats) *stats = out;
+  return rc;
 }
 
 // ---------------------------------------------------------------------------

@@ -23,6 +23,7 @@ SYMBOLS = [
     "mcx_ubench_stream", "mcx_ubench_random_rmw", "mcx_graph_insert_stats", "mcx_multi_exchange_bytes", "mcx_graph_hashtest", "mcx_hashtest_func", "mcx_debug_probe",
     "mcx_graph_infer_edges", "mcx_graph_infer_edges_dev", "mcx_graph_unitig_stats", "mcx_graph_clean",
     "mcx_graph_unitigs", "mcx_graph_unitigs_dev", "mcx_graph_pop_bubbles",
+    "mcx_graph_subgraph_begin", "mcx_graph_subgraph_seed_reads", "mcx_graph_subgraph_seed_stream_dev", "mcx_graph_subgraph_finish",
 ]
 
 
@@ -74,6 +75,15 @@ class PopStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class SubgraphStats(C.Structure):
+    """mcx_subgraph_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("num_seed_kmers", "num_seed_found", "nkmers_before", "nkmers_kept", "nkmers_removed")] + \
+               [("levels", C.c_uint32), ("narrow_launches", C.c_uint32), ("max_frontier", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class UnitigsStats(C.Structure):
     """mcx_unitigs_stats"""
     _fields_ = [(n, C.c_uint64) for n in ("num_unitigs", "num_kmers", "num_bytes", "num_cycles")]
@@ -92,6 +102,7 @@ UNITIGS_FORMATS = {"fasta": 0, "gfa": 1, "dot": 2}
 UNITIGS_POINTS = 1
 RECORDS_MUST_EXIST = 1
 INFER_POP, INFER_PRESENCE_COVG = 1, 2
+SUBGRAPH_UNITIGS, SUBGRAPH_INVERT = 1, 2
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 
 
@@ -133,6 +144,10 @@ def lib():
     L.mcx_graph_unitig_stats.argtypes = [vp, vp]
     L.mcx_graph_clean.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(CleanStats), vp]
     L.mcx_graph_pop_bubbles.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PopStats)]
+    L.mcx_graph_subgraph_begin.argtypes = [vp, C.c_uint32]
+    L.mcx_graph_subgraph_seed_reads.argtypes = [vp, vp, vp, C.c_uint64]
+    L.mcx_graph_subgraph_seed_stream_dev.argtypes = [vp, vp, C.c_uint64]
+    L.mcx_graph_subgraph_finish.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(SubgraphStats)]
     L.mcx_graph_unitigs.argtypes = [vp, C.c_int, C.c_uint32, SINK_FN, vp, C.POINTER(UnitigsStats)]
     L.mcx_graph_unitigs_dev.argtypes = [vp, C.POINTER(UnitigsArrays), C.POINTER(UnitigsStats)]
     L.mcx_graph_infer_edges.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, u64p]
@@ -477,6 +492,40 @@ class Graph:
         st = PopStats()
         _check(self.L.mcx_graph_pop_bubbles(self.h, int(max_covg), int(max_klen), int(max_kdiff), C.byref(st)))
         return st.as_dict()
+
+    def subgraph_begin(self, unitigs=False):
+        """`subgraph`, first step: set up the marks and the queue on the device (unitigs: seeds mark whole unitigs)"""
+        _check(self.L.mcx_graph_subgraph_begin(self.h, SUBGRAPH_UNITIGS if unitigs else 0))
+
+    def subgraph_seed(self, bases, offsets):
+        """mark the k-mers of the seed reads (the layout of add_reads) that are in the graph; may be repeated"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        _check(self.L.mcx_graph_subgraph_seed_reads(self.h, _ptr(bases), _ptr(offsets), len(offsets) - 1))
+
+    def subgraph_seed_stream_dev(self, d_stream, nbytes):
+        """the same for an ASCII stream in HBM (the layout of add_stream_dev)"""
+        _check(self.L.mcx_graph_subgraph_seed_stream_dev(self.h, _ptr(d_stream), int(nbytes)))
+
+    def subgraph_finish(self, dist=0, invert=False, unitigs=False):
+        """extend the marked set by `dist` edges, complement it with `invert`, prune the rest; returns the stats dict"""
+        st = SubgraphStats()
+        _check(self.L.mcx_graph_subgraph_finish(self.h, int(dist), (SUBGRAPH_UNITIGS if unitigs else 0) | (SUBGRAPH_INVERT if invert else 0),
+                                                C.byref(st)))
+        return st.as_dict()
+
+    def subgraph(self, seeds, dist=0, invert=False, unitigs=False):
+        """`subgraph` (ctx_subgraph.c): keep the k-mers within `dist` edges of the k-mers of `seeds` (a list of str or
+        bytes); with `unitigs` the seeds' whole unitigs count as seeds, with `invert` the complement is kept.
+        Returns the stats dict (num_seed_kmers, num_seed_found, nkmers_before, nkmers_kept, nkmers_removed, levels,
+        narrow_launches, max_frontier)"""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seeds]
+        offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(s) for s in seqs])
+        self.subgraph_begin(unitigs)
+        if seqs:
+            self.subgraph_seed(np.frombuffer(b"".join(seqs) or b"\n", dtype=np.uint8), offs)
+        return self.subgraph_finish(dist, invert, unitigs)
 
     def unitigs_chunks(self, format="fasta", points=False, stats=None):
         """`unitigs`: yields the text in consecutive chunks (the whole text is produced on the first step; `stats`,

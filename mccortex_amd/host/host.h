@@ -141,6 +141,7 @@ int ctx_index(int argc, char **argv);
 int ctx_infer_edges(int argc, char **argv); /* src/commands/ctx_infer_edges.c */
 int ctx_clean(int argc, char **argv);       /* src/commands/ctx_clean.c */
 int ctx_pop_bubbles(int argc, char **argv); /* src/commands/ctx_pop_bubbles.c */
+int ctx_subgraph(int argc, char **argv);    /* src/commands/ctx_subgraph.c */
 int ctx_unitigs(int argc, char **argv);     /* src/commands/ctx_unitigs.c */
 /* graph_load: one opened file's colours through its filter into the device table (cmd_clean.c) */
 struct mcx_graph;
