@@ -606,6 +606,35 @@ struct SpanGuard {
   ~SpanGuard() { if (on) (void)hipEventRecord(g->spans[idx].b, g->stream); }
 };
 
+// A grid-stride kernel over ITEMS items on `st`, in a profile span of the kernel's name; the "grid" knob caps the launch.
+// (`g` and `st` are the caller's; the enclosing function returns an MCX code.)
+static unsigned cl_grid(const mcx_graph *g, uint64_t items)
+{
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, (uint64_t)g->grid));
+}
+#define GRID_LAUNCH(NAME, ITEMS, ...)                                                            \
+  do {                                                                                           \
+    SpanGuard sp_(g, #NAME);                                                                     \
+    hipLaunchKernelGGL(NAME, dim3(cl_grid(g, ITEMS)), dim3(256), 0, st, __VA_ARGS__);            \
+    HIP_TRY(hipGetLastError());                                                                  \
+  } while (0)
+#define GRID_LAUNCH_W(NAME, ITEMS, ...)                                                          \
+  do {                                                                                           \
+    SpanGuard sp_(g, #NAME);                                                                     \
+    LAUNCH_W4(g->W, NAME, dim3(cl_grid(g, ITEMS)), dim3(256), 0, st, __VA_ARGS__);               \
+    HIP_TRY(hipGetLastError());                                                                  \
+  } while (0)
+
+// MCX_TIMING=1: host clock of a command's phases (stderr); t0 moves on to now
+static void phase_clock(const char *cmd, const char *what, double &t0)
+{
+  static const bool on = getenv("MCX_TIMING") != nullptr;
+  if (!on) return;
+  const double t = now_s();
+  fprintf(stderr, "[timing]   %s %8.1f ms  %s\n", cmd, (t - t0) * 1e3, what);
+  t0 = t;
+}
+
 template <class K> static void allow_lds(K kernel, size_t bytes)
 {
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
@@ -3157,7 +3186,7 @@ static void clean_drop(mcx_graph *g)
 }
 
 // the refusals and the closing flush; *n = k-mers in the table; `what` names the command in the messages
-static int clean_begin(mcx_graph *g, uint64_t *n, const char *what = "clean")
+static int clean_begin(mcx_graph *g, uint64_t *n, const char *what)
 {
   if (!g) return fail(MCX_ERR_ARG, "null graph");
   if (g->as_group || g->group || g->t.lbo || g->own_lbo)
@@ -3171,12 +3200,28 @@ static int clean_begin(mcx_graph *g, uint64_t *n, const char *what = "clean")
   return MCX_OK;
 }
 
-static unsigned cl_grid(const mcx_graph *g, uint64_t items)
-{
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, (uint64_t)g->grid));
-}
-
 static uint32_t cl_sort_end_bit(uint64_t n) { return 32u + (uint32_t)std::max(1, 64 - __builtin_clzll(std::max<uint64_t>(n, 1))); }
+
+// dense ids for the n k-mers of the table, into c: slot_of, map, union edges, summed coverage
+static int compact_ids(mcx_graph *g, CleanCache *c, uint64_t n)
+{
+  hipStream_t st = g->stream;
+  const uint64_t nn = std::max<uint64_t>(n, 1);
+  c->n = n;
+  HIP_TRY(c->slot_of.alloc(nn));
+  HIP_TRY(c->map.alloc(std::max<uint64_t>(g->t.nslots, 1)));
+  HIP_TRY(c->ue.alloc(nn));
+  HIP_TRY(c->cov.alloc(nn));
+  DevBuf<unsigned long long> d_cur;
+  HIP_TRY(d_cur.alloc(1));
+  HIP_TRY(hipMemsetAsync(d_cur, 0, 8, st));
+  GRID_LAUNCH(k_cl_compact, g->t.nslots, g->t, (uint32_t)g->ncols, nn, c->slot_of.p, c->map.p, c->ue.p, c->cov.p, d_cur.p);
+  unsigned long long found = 0;
+  HIP_TRY(hipMemcpyAsync(&found, d_cur, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (found != n) return fail(MCX_ERR_HIP, "table scan found %llu k-mers, counter says %llu", found, (unsigned long long)n);
+  return MCX_OK;
+}
 
 template <int W> static int unitig_stats_t(mcx_graph *g, uint64_t n, uint64_t *before)
 {
@@ -3184,7 +3229,6 @@ template <int W> static int unitig_stats_t(mcx_graph *g, uint64_t n, uint64_t *b
   clean_drop(g);
   CleanCache *c = new CleanCache;
   g->clean = c;
-  c->n = n;
   const uint64_t n2 = 2 * n, nn = std::max<uint64_t>(n, 1);
   // the whole footprint up front, so that a graph too large fails here with a clear message
   size_t sort_tmp = 0;
@@ -3197,90 +3241,47 @@ template <int W> static int unitig_stats_t(mcx_graph *g, uint64_t n, uint64_t *b
       return fail(MCX_ERR_NOMEM, "clean needs %.1f GB of device scratch for %llu k-mers, %.1f GB are free", need / 1e9,
                   (unsigned long long)n, f / 1e9);
   }
-  HIP_TRY(c->slot_of.alloc(nn));
-  HIP_TRY(c->map.alloc(std::max<uint64_t>(g->t.nslots, 1)));
-  HIP_TRY(c->cov.alloc(nn));
+  int rc = compact_ids(g, c, n);
+  if (rc != MCX_OK) return rc;
   HIP_TRY(c->uid.alloc(nn));
   HIP_TRY(c->len.alloc(nn));
   HIP_TRY(c->med.alloc(nn));
-  HIP_TRY(c->ue.alloc(nn));
   HIP_TRY(c->ends.alloc(nn));
-  DevBuf<unsigned long long> d_cur, d_hist;
+  DevBuf<unsigned long long> d_hist;
   DevBuf<uint32_t> nxt[2], mn[2], d_changed;
-  HIP_TRY(d_cur.alloc(1));
   HIP_TRY(d_hist.alloc(3 * kClBins));
-  HIP_TRY(hipMemsetAsync(d_cur, 0, 8, st));
   HIP_TRY(hipMemsetAsync(d_hist, 0, 3 * kClBins * 8, st));
-  {
-    SpanGuard sp(g, "k_cl_compact");
-    hipLaunchKernelGGL(k_cl_compact, dim3(cl_grid(g, g->t.nslots)), dim3(256), 0, st, g->t, (uint32_t)g->ncols, nn, c->slot_of.p,
-                       c->map.p, c->ue.p, c->cov.p, d_cur.p);
-  }
-  HIP_TRY(hipGetLastError());
-  unsigned long long found = 0;
-  HIP_TRY(hipMemcpyAsync(&found, d_cur, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (found != n) return fail(MCX_ERR_HIP, "table scan found %llu k-mers, counter says %llu", found, (unsigned long long)n);
   if (n) {
     // A. links, B. ranking
     for (int b = 0; b < 2; b++) { HIP_TRY(nxt[b].alloc(n2)); HIP_TRY(mn[b].alloc(n2)); }
     HIP_TRY(c->lk.alloc(n));
     HIP_TRY(d_changed.alloc(1));
-    {
-      SpanGuard sp(g, "k_cl_links");
-      LAUNCH_W4(g->W, k_cl_links, dim3(cl_grid(g, n)), dim3(256), 0, st, g->t, g->k, n, c->slot_of.p, c->map.p, c->ue.p, c->lk.p,
-                nxt[0].p, mn[0].p);
-    }
-    HIP_TRY(hipGetLastError());
+    GRID_LAUNCH_W(k_cl_links, n, g->t, g->k, n, c->slot_of.p, c->map.p, c->ue.p, c->lk.p, nxt[0].p, mn[0].p);
     int cur = 0;
     for (int round = 0;; round++) {
       if (round > 40) return fail(MCX_ERR_HIP, "unitig ranking did not settle");  // 2^40 steps exceed any chain of < 2^31 k-mers
       uint32_t changed = 0;
       HIP_TRY(hipMemsetAsync(d_changed, 0, 4, st));
-      {
-        SpanGuard sp(g, "k_cl_jump");
-        hipLaunchKernelGGL(k_cl_jump, dim3(cl_grid(g, n2)), dim3(256), 0, st, n2, c->lk.p, nxt[cur].p, mn[cur].p, nxt[cur ^ 1].p,
-                           mn[cur ^ 1].p, d_changed.p);
-      }
-      HIP_TRY(hipGetLastError());
+      GRID_LAUNCH(k_cl_jump, n2, n2, c->lk.p, nxt[cur].p, mn[cur].p, nxt[cur ^ 1].p, mn[cur ^ 1].p, d_changed.p);
       HIP_TRY(hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
       cur ^= 1;
       if (!changed) break;
     }
     HIP_TRY(hipMemsetAsync(c->len, 0, n * 4, st));
-    {
-      SpanGuard sp(g, "k_cl_unitig");
-      hipLaunchKernelGGL(k_cl_unitig, dim3(cl_grid(g, n)), dim3(256), 0, st, n, nxt[cur].p, mn[cur].p, c->lk.p, c->ue.p, c->uid.p,
-                         c->len.p, c->ends.p);
-    }
-    HIP_TRY(hipGetLastError());
+    GRID_LAUNCH(k_cl_unitig, n, n, nxt[cur].p, mn[cur].p, c->lk.p, c->ue.p, c->uid.p, c->len.p, c->ends.p);
     // C. medians: sorting (unitig id << 32 | coverage) puts each unitig's coverages together, in order.  The two
     // nxt arrays (8 n bytes each) hold the keys now.
     uint64_t *keys = reinterpret_cast<uint64_t *>(nxt[0].p), *sorted = reinterpret_cast<uint64_t *>(nxt[1].p);
-    {
-      SpanGuard sp(g, "k_cl_keys");
-      hipLaunchKernelGGL(k_cl_keys, dim3(cl_grid(g, n)), dim3(256), 0, st, n, c->uid.p, c->cov.p, keys);
-    }
-    HIP_TRY(hipGetLastError());
+    GRID_LAUNCH(k_cl_keys, n, n, c->uid.p, c->cov.p, keys);
     DevBuf<uint8_t> tmp;
     HIP_TRY(tmp.alloc(std::max<size_t>(sort_tmp, 1)));
     {
       SpanGuard sp(g, "radix_sort_keys");
       HIP_TRY(rocprim::radix_sort_keys((void *)tmp.p, sort_tmp, keys, sorted, n, 0, cl_sort_end_bit(n), st));
     }
-    {
-      SpanGuard sp(g, "k_cl_median");
-      hipLaunchKernelGGL(k_cl_median, dim3(cl_grid(g, n)), dim3(256), 0, st, n, (const uint64_t *)sorted, c->len.p, c->med.p,
-                         d_hist.p + kClBins);
-    }
-    HIP_TRY(hipGetLastError());
-    {
-      SpanGuard sp(g, "k_cl_kmer_hist");
-      hipLaunchKernelGGL(k_cl_kmer_hist, dim3(cl_grid(g, n)), dim3(256), 0, st, n, c->cov.p, c->uid.p, (const uint8_t *)nullptr,
-                         d_hist.p);
-    }
-    HIP_TRY(hipGetLastError());
+    GRID_LAUNCH(k_cl_median, n, n, (const uint64_t *)sorted, c->len.p, c->med.p, d_hist.p + kClBins);
+    GRID_LAUNCH(k_cl_kmer_hist, n, n, c->cov.p, c->uid.p, (const uint8_t *)nullptr, d_hist.p);
     HIP_TRY(hipStreamSynchronize(st));  // before the scratch is freed
   }
   if (before) HIP_TRY(hipMemcpyAsync(before, d_hist, 3 * kClBins * 8, hipMemcpyDeviceToHost, st));
@@ -3291,7 +3292,7 @@ template <int W> static int unitig_stats_t(mcx_graph *g, uint64_t n, uint64_t *b
 extern "C" int mcx_graph_unitig_stats(mcx_graph *g, uint64_t *before)
 {
   uint64_t n = 0, cs = 0;
-  int rc = clean_begin(g, &n);
+  int rc = clean_begin(g, &n, "clean");
   if (rc == MCX_OK) rc = mcx_graph_checksum(g, &cs, nullptr);
   if (rc != MCX_OK) return rc;
   switch (g->W) {
@@ -3305,16 +3306,32 @@ extern "C" int mcx_graph_unitig_stats(mcx_graph *g, uint64_t *before)
   return rc;
 }
 
+// How every command that works on the decomposition starts.  The refusals and the closing flush, in the name `what`
+// (*n = k-mers in the table); then `admit`, the caller's check of its own arguments, if it has one; then the test
+// whether the kept decomposition describes the table as it is now: any insert, record load, inferedges, intersect or
+// prune since then changes the count or the checksum over keys, coverage and edges.  With `build` the passes run again
+// when it does not.  *current: g->clean is the decomposition of this table.
+static int ensure_decomposition(mcx_graph *g, const char *what, bool build, uint64_t *n, bool *current = nullptr,
+                                const std::function<int()> &admit = nullptr)
+{
+  uint64_t cs = 0;
+  int rc = clean_begin(g, n, what);
+  if (rc == MCX_OK && admit) rc = admit();
+  if (rc == MCX_OK) rc = mcx_graph_checksum(g, &cs, nullptr);
+  if (rc != MCX_OK) return rc;
+  bool cur = g->clean && g->clean->n == *n && g->clean->checksum == cs;
+  if (!cur && build) {
+    if ((rc = mcx_graph_unitig_stats(g, nullptr)) != MCX_OK) return rc;
+    cur = true;
+  }
+  if (current) *current = cur;
+  return MCX_OK;
+}
+
 extern "C" int mcx_graph_clean(mcx_graph *g, uint32_t covg_threshold, uint32_t min_keep_tip, mcx_clean_stats *stats, uint64_t *after)
 {
   uint64_t n = 0;
-  int rc = clean_begin(g, &n);
-  if (rc != MCX_OK) return rc;
-  // The decomposition is used only if it describes the table as it is now: any insert, record load, inferedges or
-  // intersect since then changes the count or the checksum over keys, coverage and edges, and the passes run again.
-  uint64_t cs = 0;
-  rc = mcx_graph_checksum(g, &cs, nullptr);
-  if (rc == MCX_OK && (!g->clean || g->clean->n != n || g->clean->checksum != cs)) rc = mcx_graph_unitig_stats(g, nullptr);
+  int rc = ensure_decomposition(g, "clean", true, &n);
   if (rc != MCX_OK) return rc;
   CleanCache *c = g->clean;
   hipStream_t st = g->stream;
@@ -3326,30 +3343,10 @@ extern "C" int mcx_graph_clean(mcx_graph *g, uint32_t covg_threshold, uint32_t m
   HIP_TRY(hipMemsetAsync(d_st, 0, 8 * 8, st));
   HIP_TRY(hipMemsetAsync(d_hist, 0, 3 * kClBins * 8, st));
   if (n) {
-    {
-      SpanGuard sp(g, "k_cl_decide");
-      hipLaunchKernelGGL(k_cl_decide, dim3(cl_grid(g, n)), dim3(256), 0, st, n, c->len.p, c->med.p, c->ends.p, covg_threshold,
-                         min_keep_tip, keep.p, d_st.p, d_hist.p + kClBins);
-    }
-    HIP_TRY(hipGetLastError());
-    {
-      SpanGuard sp(g, "k_cl_kmer_hist");
-      hipLaunchKernelGGL(k_cl_kmer_hist, dim3(cl_grid(g, n)), dim3(256), 0, st, n, c->cov.p, c->uid.p, (const uint8_t *)keep.p,
-                         d_hist.p);
-    }
-    HIP_TRY(hipGetLastError());
-    {
-      SpanGuard sp(g, "k_cl_prune_edges");
-      LAUNCH_W4(g->W, k_cl_prune_edges, dim3(cl_grid(g, n)), dim3(256), 0, st, g->t, g->k, (uint32_t)g->ncols, n, c->slot_of.p,
-                c->map.p, c->ue.p, c->uid.p, keep.p);
-    }
-    HIP_TRY(hipGetLastError());
-    {
-      SpanGuard sp(g, "k_cl_tombstone");
-      hipLaunchKernelGGL(k_cl_tombstone, dim3(cl_grid(g, n)), dim3(256), 0, st, g->t, n, c->slot_of.p, c->uid.p, keep.p, g->d_ctr,
-                         d_st.p + 6);
-    }
-    HIP_TRY(hipGetLastError());
+    GRID_LAUNCH(k_cl_decide, n, n, c->len.p, c->med.p, c->ends.p, covg_threshold, min_keep_tip, keep.p, d_st.p, d_hist.p + kClBins);
+    GRID_LAUNCH(k_cl_kmer_hist, n, n, c->cov.p, c->uid.p, (const uint8_t *)keep.p, d_hist.p);
+    GRID_LAUNCH_W(k_cl_prune_edges, n, g->t, g->k, (uint32_t)g->ncols, n, c->slot_of.p, c->map.p, c->ue.p, c->uid.p, keep.p);
+    GRID_LAUNCH(k_cl_tombstone, n, g->t, n, c->slot_of.p, c->uid.p, keep.p, g->d_ctr, d_st.p + 6);
   }
   unsigned long long h[8];
   HIP_TRY(hipMemcpyAsync(h, d_st, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -3368,38 +3365,13 @@ extern "C" int mcx_graph_clean(mcx_graph *g, uint32_t covg_threshold, uint32_t m
 // ---------------------------------------------------------------------------
 // popbubbles (ctx_pop_bubbles.c, pop_bubbles.c): sums and ends, pairs, turns, prune -- mcx_pop.h
 // ---------------------------------------------------------------------------
-#define POP_LAUNCH(NAME, ITEMS, ...)                                                             \
-  do {                                                                                           \
-    SpanGuard sp_(g, #NAME);                                                                     \
-    hipLaunchKernelGGL(NAME, dim3(cl_grid(g, ITEMS)), dim3(256), 0, st, __VA_ARGS__);            \
-    HIP_TRY(hipGetLastError());                                                                  \
-  } while (0)
-#define POP_LAUNCH_W(NAME, ITEMS, ...)                                                           \
-  do {                                                                                           \
-    SpanGuard sp_(g, #NAME);                                                                     \
-    LAUNCH_W4(g->W, NAME, dim3(cl_grid(g, ITEMS)), dim3(256), 0, st, __VA_ARGS__);               \
-    HIP_TRY(hipGetLastError());                                                                  \
-  } while (0)
-
-static void pop_clock(const char *what, double &t0)
-{
-  static const bool on = getenv("MCX_TIMING") != nullptr;
-  if (!on) return;
-  const double t = now_s();
-  fprintf(stderr, "[timing]   popbubbles %8.1f ms  %s\n", (t - t0) * 1e3, what);
-  t0 = t;
-}
-
 extern "C" int mcx_graph_pop_bubbles(mcx_graph *g, int32_t max_covg, int32_t max_klen, int32_t max_kdiff, mcx_pop_stats *stats)
 {
-  uint64_t n = 0, cs = 0;
-  int rc = clean_begin(g, &n, "popbubbles");
-  if (rc == MCX_OK) rc = mcx_graph_checksum(g, &cs, nullptr);
+  uint64_t n = 0;
   double t0 = now_s();
-  // the decomposition is reused when it describes the table as it is now (the test mcx_graph_clean makes)
-  if (rc == MCX_OK && (!g->clean || g->clean->n != n || g->clean->checksum != cs)) rc = mcx_graph_unitig_stats(g, nullptr);
+  int rc = ensure_decomposition(g, "popbubbles", true, &n);
   if (rc != MCX_OK) return rc;
-  pop_clock("decomposition (reused when it is current)", t0);
+  phase_clock("popbubbles", "decomposition (reused when it is current)", t0);
   mcx_pop_stats out;
   memset(&out, 0, sizeof(out));
   out.nkmers_before = n;
@@ -3435,14 +3407,14 @@ extern "C" int mcx_graph_pop_bubbles(mcx_graph *g, int32_t max_covg, int32_t max
   HIP_TRY(hipMemsetAsync(d_cnt, 0, 4 * 8, st));
   HIP_TRY(hipMemsetAsync(d_flag, 0, 2 * 4, st));
   // A. sums and ends
-  POP_LAUNCH(k_pop_sums, n, n, (const uint32_t *)c->uid.p, (const uint32_t *)c->cov.p, (const uint8_t *)c->lk.p, sum.p, ends.p);
-  POP_LAUNCH_W(k_pop_norm, n, g->t, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->len.p, ends.p);
+  GRID_LAUNCH(k_pop_sums, n, n, (const uint32_t *)c->uid.p, (const uint32_t *)c->cov.p, (const uint8_t *)c->lk.p, sum.p, ends.p);
+  GRID_LAUNCH_W(k_pop_norm, n, g->t, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->len.p, ends.p);
   if (getenv("MCX_TIMING")) HIP_TRY(hipStreamSynchronize(st));
-  pop_clock("sums and ends", t0);
+  phase_clock("popbubbles", "sums and ends", t0);
   // B. pairs: counted first (nothing is stored), then stored into a list of exactly that size
-  POP_LAUNCH_W(k_pop_pairs, n, g->t, g->k, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p, (const uint8_t *)c->ue.p,
-               (const uint32_t *)c->uid.p, (const uint32_t *)c->len.p, (const uint8_t *)c->lk.p, (const uint32_t *)ends.p, (uint64_t)0,
-               (uint64_t *)nullptr, d_cnt.p, d_flag.p);
+  GRID_LAUNCH_W(k_pop_pairs, n, g->t, g->k, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p, (const uint8_t *)c->ue.p,
+                (const uint32_t *)c->uid.p, (const uint32_t *)c->len.p, (const uint8_t *)c->lk.p, (const uint32_t *)ends.p, (uint64_t)0,
+                (uint64_t *)nullptr, d_cnt.p, d_flag.p);
   unsigned long long np = 0;
   uint32_t inside = 0;
   HIP_TRY(hipMemcpyAsync(&np, d_cnt, 8, hipMemcpyDeviceToHost, st));
@@ -3456,49 +3428,49 @@ extern "C" int mcx_graph_pop_bubbles(mcx_graph *g, int32_t max_covg, int32_t max
       return fail(MCX_ERR_NOMEM, "popbubbles found %llu parallel pairs (%.1f GB), %.1f GB of HBM are free", np, np * 8 / 1e9, fr / 1e9);
     HIP_TRY(pairs.alloc(np));
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, st));
-    POP_LAUNCH_W(k_pop_pairs, n, g->t, g->k, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p, (const uint8_t *)c->ue.p,
-                 (const uint32_t *)c->uid.p, (const uint32_t *)c->len.p, (const uint8_t *)c->lk.p, (const uint32_t *)ends.p, (uint64_t)np,
-                 pairs.p, d_cnt.p, d_flag.p);
+    GRID_LAUNCH_W(k_pop_pairs, n, g->t, g->k, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p, (const uint8_t *)c->ue.p,
+                  (const uint32_t *)c->uid.p, (const uint32_t *)c->len.p, (const uint8_t *)c->lk.p, (const uint32_t *)ends.p, (uint64_t)np,
+                  pairs.p, d_cnt.p, d_flag.p);
     unsigned long long np2 = 0;
     HIP_TRY(hipMemcpyAsync(&np2, d_cnt, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (np2 != np) return fail(MCX_ERR_HIP, "the two passes over the parallel pairs disagree (%llu, %llu)", np, np2);
   }
-  pop_clock("pairs", t0);
+  phase_clock("popbubbles", "pairs", t0);
   out.num_pairs = np;
   unsigned long long h[4] = {np, 0, 0, 0};
   if (np) {
-    POP_LAUNCH(k_pop_mark, np, np, pairs.p, (const unsigned long long *)sum.p, (const uint32_t *)c->len.p, max_covg, max_klen, max_kdiff);
+    GRID_LAUNCH(k_pop_mark, np, np, pairs.p, (const unsigned long long *)sum.p, (const uint32_t *)c->len.p, max_covg, max_klen, max_kdiff);
     // C. turns: a round decides every unitig whose possible removers are all decided; the relation leads from
     // lower to higher E, so each round decides at least the undecided unitig with the lowest E
     for (uint64_t round = 0;; round++) {
       if (round > n + 1) return fail(MCX_ERR_HIP, "the order resolution did not settle");
       uint32_t changed = 0;
       HIP_TRY(hipMemsetAsync(d_flag.p + 1, 0, 4, st));
-      POP_LAUNCH(k_pop_threats, np, np, (const uint64_t *)pairs.p, (const uint8_t *)state.p, kill.p, wait.p);
-      POP_LAUNCH(k_pop_settle, n, n, (const uint32_t *)c->len.p, state.p, (const uint8_t *)kill.p, wait.p, d_flag.p + 1);
+      GRID_LAUNCH(k_pop_threats, np, np, (const uint64_t *)pairs.p, (const uint8_t *)state.p, kill.p, wait.p);
+      GRID_LAUNCH(k_pop_settle, n, n, (const uint32_t *)c->len.p, state.p, (const uint8_t *)kill.p, wait.p, d_flag.p + 1);
       HIP_TRY(hipMemcpyAsync(&changed, d_flag.p + 1, 4, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
       if (!changed) break;
       out.rounds++;
     }
     // D. losers
-    POP_LAUNCH(k_pop_apply, np, np, (const uint64_t *)pairs.p, (const unsigned long long *)sum.p, (const uint32_t *)c->len.p, max_covg,
-               max_klen, max_kdiff, (const uint8_t *)state.p, keep.p, d_cnt.p + 1);
-    POP_LAUNCH(k_pop_count, n, n, (const uint32_t *)c->len.p, (const uint8_t *)keep.p, d_cnt.p + 2);
+    GRID_LAUNCH(k_pop_apply, np, np, (const uint64_t *)pairs.p, (const unsigned long long *)sum.p, (const uint32_t *)c->len.p, max_covg,
+                max_klen, max_kdiff, (const uint8_t *)state.p, keep.p, d_cnt.p + 1);
+    GRID_LAUNCH(k_pop_count, n, n, (const uint32_t *)c->len.p, (const uint8_t *)keep.p, d_cnt.p + 2);
     HIP_TRY(hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    pop_clock("resolution", t0);
+    phase_clock("popbubbles", "resolution", t0);
   }
   if (h[2]) {
-    POP_LAUNCH_W(k_cl_prune_edges, n, g->t, g->k, (uint32_t)g->ncols, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p,
-                 (const uint8_t *)c->ue.p, (const uint32_t *)c->uid.p, (const uint8_t *)keep.p);
-    POP_LAUNCH(k_cl_tombstone, n, g->t, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint8_t *)keep.p, g->d_ctr,
-               d_cnt.p + 3);
+    GRID_LAUNCH_W(k_cl_prune_edges, n, g->t, g->k, (uint32_t)g->ncols, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p,
+                  (const uint8_t *)c->ue.p, (const uint32_t *)c->uid.p, (const uint8_t *)keep.p);
+    GRID_LAUNCH(k_cl_tombstone, n, g->t, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint8_t *)keep.p, g->d_ctr,
+                d_cnt.p + 3);
     HIP_TRY(hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     clean_drop(g);  // the decomposition described the graph before the prune
-    pop_clock("prune", t0);
+    phase_clock("popbubbles", "prune", t0);
   }
   out.num_popped = h[1];
   out.num_unitigs_removed = h[2];
@@ -3539,18 +3511,15 @@ constexpr uint32_t kSgLevelsPerRead = 8;  // wide levels chained on the stream b
 
 extern "C" int mcx_graph_subgraph_begin(mcx_graph *g, uint32_t flags)
 {
-  uint64_t n = 0, cs = 0;
-  int rc = clean_begin(g, &n, "subgraph");
+  uint64_t n = 0;
+  bool current = false;
+  // (without --unitigs the dense ids are enough: nothing is built here)
+  int rc = ensure_decomposition(g, "subgraph", (flags & MCX_SUBGRAPH_UNITIGS) != 0, &n, &current, [&]() -> int {
+    if (flags & ~(uint32_t)(MCX_SUBGRAPH_UNITIGS | MCX_SUBGRAPH_INVERT)) return fail(MCX_ERR_ARG, "subgraph: unknown flags 0x%x", flags);
+    subgraph_drop(g);  // a second begin starts over
+    return MCX_OK;
+  });
   if (rc != MCX_OK) return rc;
-  if (flags & ~(uint32_t)(MCX_SUBGRAPH_UNITIGS | MCX_SUBGRAPH_INVERT)) return fail(MCX_ERR_ARG, "subgraph: unknown flags 0x%x", flags);
-  subgraph_drop(g);
-  rc = mcx_graph_checksum(g, &cs, nullptr);
-  if (rc != MCX_OK) return rc;
-  bool current = g->clean && g->clean->n == n && g->clean->checksum == cs;
-  if (!current && (flags & MCX_SUBGRAPH_UNITIGS)) {
-    if ((rc = mcx_graph_unitig_stats(g, nullptr)) != MCX_OK) return rc;
-    current = true;
-  }
   const uint64_t nn = std::max<uint64_t>(n, 1), nslots = std::max<uint64_t>(g->t.nslots, 1);
   {
     size_t fr = 0, tot = 0;
@@ -3571,25 +3540,9 @@ extern "C" int mcx_graph_subgraph_begin(mcx_graph *g, uint32_t flags)
       s->ids = g->clean;
       g->clean = nullptr;
     } else {
-      CleanCache *c = s->ids = new CleanCache;
-      c->n = n;
-      HIP_TRY(c->slot_of.alloc(nn));
-      HIP_TRY(c->map.alloc(nslots));
-      HIP_TRY(c->ue.alloc(nn));
-      HIP_TRY(c->cov.alloc(nn));
-      DevBuf<unsigned long long> d_cur;
-      HIP_TRY(d_cur.alloc(1));
-      HIP_TRY(hipMemsetAsync(d_cur, 0, 8, st));
-      {
-        SpanGuard sp(g, "k_cl_compact");
-        hipLaunchKernelGGL(k_cl_compact, dim3(cl_grid(g, g->t.nslots)), dim3(256), 0, st, g->t, (uint32_t)g->ncols, nn, c->slot_of.p,
-                           c->map.p, c->ue.p, c->cov.p, d_cur.p);
-      }
-      HIP_TRY(hipGetLastError());
-      unsigned long long found = 0;
-      HIP_TRY(hipMemcpyAsync(&found, d_cur, 8, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (found != n) return fail(MCX_ERR_HIP, "table scan found %llu k-mers, counter says %llu", found, (unsigned long long)n);
+      s->ids = new CleanCache;
+      int rc2 = compact_ids(g, s->ids, n);
+      if (rc2 != MCX_OK) return rc2;
     }
     const uint64_t words = (nn + 31) / 32;
     HIP_TRY(s->mark.alloc(words));
@@ -3721,7 +3674,7 @@ extern "C" int mcx_graph_subgraph_finish(mcx_graph *g, uint32_t dist, uint32_t f
   };
   auto run = [&]() -> int {
     if (s->flags & MCX_SUBGRAPH_UNITIGS)
-      POP_LAUNCH(k_sg_grab, n, v, (const uint32_t *)s->ids->uid.p, (const uint8_t *)s->uflag.p, s->cnt.p);
+      GRID_LAUNCH(k_sg_grab, n, v, (const uint32_t *)s->ids->uid.p, (const uint8_t *)s->uflag.p, s->cnt.p);
     hipLaunchKernelGGL(k_sg_open, dim3(1), dim3(1), 0, st, s->ctl.p);
     HIP_TRY(hipGetLastError());
     int rc2 = read_ctl();
@@ -3747,8 +3700,8 @@ extern "C" int mcx_graph_subgraph_finish(mcx_graph *g, uint32_t dist, uint32_t f
     }
     // C. the prune
     if (n) {
-      POP_LAUNCH_W(k_sg_prune_edges, n, g->t, g->k, (uint32_t)g->ncols, v, invert);
-      POP_LAUNCH(k_sg_tombstone, n, g->t, v, invert, g->d_ctr, s->cnt.p + 2);
+      GRID_LAUNCH_W(k_sg_prune_edges, n, g->t, g->k, (uint32_t)g->ncols, v, invert);
+      GRID_LAUNCH(k_sg_tombstone, n, g->t, v, invert, g->d_ctr, s->cnt.p + 2);
     }
     unsigned long long h[3];
     HIP_TRY(hipMemcpyAsync(h, s->cnt, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -3780,15 +3733,6 @@ struct UnWork {
   DevBuf<uint64_t> uoff, eoff;
 };
 
-static void un_clock(const char *what, double &t0)
-{
-  static const bool on = getenv("MCX_TIMING") != nullptr;
-  if (!on) return;
-  const double t = now_s();
-  fprintf(stderr, "[timing]   unitigs %8.1f ms  %s\n", (t - t0) * 1e3, what);
-  t0 = t;
-}
-
 template <class In> static int un_scan(mcx_graph *g, const In *in, uint64_t *out, uint64_t cnt)
 {
   size_t tmp_bytes = 0;
@@ -3800,19 +3744,6 @@ template <class In> static int un_scan(mcx_graph *g, const In *in, uint64_t *out
   return MCX_OK;
 }
 
-#define UN_LAUNCH(NAME, ITEMS, ...)                                                              \
-  do {                                                                                           \
-    SpanGuard sp_(g, #NAME);                                                                     \
-    hipLaunchKernelGGL(NAME, dim3(cl_grid(g, ITEMS)), dim3(256), 0, st, __VA_ARGS__);            \
-    HIP_TRY(hipGetLastError());                                                                  \
-  } while (0)
-#define UN_LAUNCH_W(NAME, ITEMS, ...)                                                            \
-  do {                                                                                           \
-    SpanGuard sp_(g, #NAME);                                                                     \
-    LAUNCH_W4(g->W, NAME, dim3(cl_grid(g, ITEMS)), dim3(256), 0, st, __VA_ARGS__);               \
-    HIP_TRY(hipGetLastError());                                                                  \
-  } while (0)
-
 // pointer jumping until a round finishes no node
 static int un_jump(mcx_graph *g, uint64_t m, const uint32_t *list, const uint8_t *lk, uint64_t *pk, uint32_t *d_changed)
 {
@@ -3821,7 +3752,7 @@ static int un_jump(mcx_graph *g, uint64_t m, const uint32_t *list, const uint8_t
     if (round > 40) return fail(MCX_ERR_HIP, "unitig ranking did not settle");  // (rounds halve the distance left: 31 suffice)
     uint32_t changed = 0;
     HIP_TRY(hipMemsetAsync(d_changed, 0, 4, st));
-    UN_LAUNCH(k_un_jump, m, m, list, lk, pk, d_changed);
+    GRID_LAUNCH(k_un_jump, m, m, list, lk, pk, d_changed);
     HIP_TRY(hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (!changed) return MCX_OK;
@@ -3831,11 +3762,8 @@ static int un_jump(mcx_graph *g, uint64_t m, const uint32_t *list, const uint8_t
 // A. rank and B. order; fmt < 0: no text is wanted (no record lengths beyond FASTA's, no edge lines)
 static int unitigs_prepare(mcx_graph *g, int fmt, UnWork &w)
 {
-  uint64_t n = 0, cs = 0;
-  int rc = clean_begin(g, &n);
-  if (rc == MCX_OK) rc = mcx_graph_checksum(g, &cs, nullptr);
-  // the decomposition is reused when it describes the table as it is now (the test mcx_graph_clean makes)
-  if (rc == MCX_OK && (!g->clean || g->clean->n != n || g->clean->checksum != cs)) rc = mcx_graph_unitig_stats(g, nullptr);
+  uint64_t n = 0;
+  int rc = ensure_decomposition(g, "clean", true, &n);
   if (rc != MCX_OK) return rc;
   w.n = n;
   if (!n) return MCX_OK;
@@ -3855,31 +3783,31 @@ static int unitigs_prepare(mcx_graph *g, int fmt, UnWork &w)
   HIP_TRY(d_changed.alloc(1));
   HIP_TRY(d_cnt.alloc(4));
   HIP_TRY(hipMemsetAsync(d_cnt, 0, 4 * 8, st));
-  UN_LAUNCH_W(k_cl_links, n, g->t, g->k, n, c->slot_of.p, c->map.p, c->ue.p, lk.p, nxt0.p, list.p);
-  UN_LAUNCH(k_un_init, n2, n2, (const uint32_t *)nxt0.p, pk.p);
+  GRID_LAUNCH_W(k_cl_links, n, g->t, g->k, n, c->slot_of.p, c->map.p, c->ue.p, lk.p, nxt0.p, list.p);
+  GRID_LAUNCH(k_un_init, n2, n2, (const uint32_t *)nxt0.p, pk.p);
   if ((rc = un_jump(g, n2, nullptr, lk, pk, d_changed)) != MCX_OK) return rc;
-  UN_LAUNCH(k_un_mark, n, n, lk.p, (const uint64_t *)pk.p, list.p, d_cnt.p);
+  GRID_LAUNCH(k_un_mark, n, n, lk.p, (const uint64_t *)pk.p, list.p, d_cnt.p);
   unsigned long long h_cnt[4] = {0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  un_clock("chains ranked", t0);
+  phase_clock("unitigs", "chains ranked", t0);
   if (const uint64_t m = h_cnt[0]) {  // oriented nodes on closed cycles
     HIP_TRY(mk.alloc(n));
     for (uint32_t wd = 0; wd < (uint32_t)g->W; wd++) {
-      UN_LAUNCH(k_un_cyc_reset, m, m, (const uint32_t *)list.p, (const uint32_t *)c->uid.p, mk.p);
-      UN_LAUNCH(k_un_cyc_min, m, g->t, m, (const uint32_t *)list.p, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint8_t *)lk.p, wd, mk.p);
-      UN_LAUNCH(k_un_cyc_keep, m, g->t, m, (const uint32_t *)list.p, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, lk.p, wd, (const unsigned long long *)mk.p);
+      GRID_LAUNCH(k_un_cyc_reset, m, m, (const uint32_t *)list.p, (const uint32_t *)c->uid.p, mk.p);
+      GRID_LAUNCH(k_un_cyc_min, m, g->t, m, (const uint32_t *)list.p, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint8_t *)lk.p, wd, mk.p);
+      GRID_LAUNCH(k_un_cyc_keep, m, g->t, m, (const uint32_t *)list.p, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, lk.p, wd, (const unsigned long long *)mk.p);
     }
-    UN_LAUNCH(k_un_cut, m, m, (const uint32_t *)list.p, (const uint32_t *)nxt0.p, lk.p, d_cnt.p + 1);
-    UN_LAUNCH(k_un_reinit, m, m, (const uint32_t *)list.p, (const uint32_t *)nxt0.p, (const uint8_t *)lk.p, pk.p);
+    GRID_LAUNCH(k_un_cut, m, m, (const uint32_t *)list.p, (const uint32_t *)nxt0.p, lk.p, d_cnt.p + 1);
+    GRID_LAUNCH(k_un_reinit, m, m, (const uint32_t *)list.p, (const uint32_t *)nxt0.p, (const uint8_t *)lk.p, pk.p);
     if ((rc = un_jump(g, m, list, lk, pk, d_changed)) != MCX_OK) return rc;
-    un_clock("cycles cut and ranked", t0);
+    phase_clock("unitigs", "cycles cut and ranked", t0);
   }
   // B. order
   HIP_TRY(head.alloc(n));
   HIP_TRY(starts.alloc(n));
   HIP_TRY(hipMemsetAsync(head, 0, n * 4, st));  // (every unitig id gets its head below; a missing one must not point outside)
-  UN_LAUNCH_W(k_un_heads, n, g->t, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint64_t *)pk.p, head.p, starts.p, d_cnt.p + 2);
+  GRID_LAUNCH_W(k_un_heads, n, g->t, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint64_t *)pk.p, head.p, starts.p, d_cnt.p + 2);
   HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const uint64_t nu = h_cnt[2];
@@ -3897,7 +3825,7 @@ static int unitigs_prepare(mcx_graph *g, int fmt, UnWork &w)
     HIP_TRY(tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
     uint64_t *cur = starts.p, *nxt = sorted.p;
     for (int wd = g->W - 1; wd >= 0; wd--) {
-      UN_LAUNCH(k_un_keyword, nu, g->t, nu, (const uint64_t *)c->slot_of.p, (const uint64_t *)cur, (uint32_t)wd, ks.p);
+      GRID_LAUNCH(k_un_keyword, nu, g->t, nu, (const uint64_t *)c->slot_of.p, (const uint64_t *)cur, (uint32_t)wd, ks.p);
       SpanGuard sp(g, "radix_sort_pairs");
       HIP_TRY(rocprim::radix_sort_pairs((void *)tmp.p, tmp_bytes, ks.p, ks2.p, cur, nxt, nu, 0, wd ? 64 : 2 * g->k - 64 * (g->W - 1), st));
       std::swap(cur, nxt);
@@ -3914,15 +3842,15 @@ static int unitigs_prepare(mcx_graph *g, int fmt, UnWork &w)
   HIP_TRY(w.uoff.alloc(nu + 1));
   HIP_TRY(w.ubase.alloc(nu + 1));
   HIP_TRY(hipMemsetAsync(w.uoff.p + nu, 0, 8, st));
-  UN_LAUNCH(k_un_number, nu, nu, tfmt, g->k, (const uint64_t *)sorted.p, (const uint32_t *)c->uid.p, (const uint32_t *)c->len.p, (const uint32_t *)head.p,
-            (const uint64_t *)pk.p, (const uint8_t *)c->ue.p, unum.p, w.ufirst.p, w.ulast.p, w.ulen.p, w.upn.p, w.uoff.p);
+  GRID_LAUNCH(k_un_number, nu, nu, tfmt, g->k, (const uint64_t *)sorted.p, (const uint32_t *)c->uid.p, (const uint32_t *)c->len.p, (const uint32_t *)head.p,
+              (const uint64_t *)pk.p, (const uint8_t *)c->ue.p, unum.p, w.ufirst.p, w.ulast.p, w.ulen.p, w.upn.p, w.uoff.p);
   if ((rc = un_scan(g, (const uint64_t *)w.uoff.p, w.uoff.p, nu + 1)) != MCX_OK) return rc;
   {
     // positions in the base array: fewer than 2^31 k-mers, so 32 bits hold them (scanned in 64, narrowed by ks)
     DevBuf<uint64_t> b64;
     HIP_TRY(b64.alloc(nu + 1));
     if ((rc = un_scan(g, (const uint32_t *)w.ulen.p, b64.p, nu)) != MCX_OK) return rc;
-    UN_LAUNCH(k_un_narrow, nu, nu, (const uint64_t *)b64.p, w.ubase.p);
+    GRID_LAUNCH(k_un_narrow, nu, nu, (const uint64_t *)b64.p, w.ubase.p);
     HIP_TRY(hipStreamSynchronize(st));
   }
   HIP_TRY(hipMemcpyAsync(&w.unit_bytes, w.uoff.p + nu, 8, hipMemcpyDeviceToHost, st));
@@ -3930,22 +3858,22 @@ static int unitigs_prepare(mcx_graph *g, int fmt, UnWork &w)
   HIP_TRY(w.krk.alloc(n));
   HIP_TRY(w.kori.alloc(n));
   HIP_TRY(w.bases.alloc(n));
-  UN_LAUNCH_W(k_un_place, n, g->t, g->k, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint32_t *)head.p, (const uint32_t *)unum.p,
-              (const uint64_t *)pk.p, (const uint32_t *)w.ubase.p, w.kun.p, w.krk.p, w.kori.p, w.bases.p);
+  GRID_LAUNCH_W(k_un_place, n, g->t, g->k, n, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->uid.p, (const uint32_t *)head.p, (const uint32_t *)unum.p,
+                (const uint64_t *)pk.p, (const uint32_t *)w.ubase.p, w.kun.p, w.krk.p, w.kori.p, w.bases.p);
   if (fmt == kUnGfa || fmt == kUnDot) {
     DevBuf<uint8_t> elen;
     HIP_TRY(w.etgt.alloc(8 * nu));
     HIP_TRY(elen.alloc(8 * nu + 1));
     HIP_TRY(w.eoff.alloc(8 * nu + 1));
     HIP_TRY(hipMemsetAsync(elen.p + 8 * nu, 0, 1, st));
-    UN_LAUNCH_W(k_un_edges, 2 * nu, g->t, g->k, fmt, nu, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p, (const uint8_t *)c->ue.p,
-                (const uint32_t *)w.ufirst.p, (const uint32_t *)w.ulast.p, (const uint32_t *)w.kun.p, (const uint32_t *)w.krk.p,
-                (const uint8_t *)w.kori.p, w.etgt.p, elen.p);
+    GRID_LAUNCH_W(k_un_edges, 2 * nu, g->t, g->k, fmt, nu, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p, (const uint8_t *)c->ue.p,
+                  (const uint32_t *)w.ufirst.p, (const uint32_t *)w.ulast.p, (const uint32_t *)w.kun.p, (const uint32_t *)w.krk.p,
+                  (const uint8_t *)w.kori.p, w.etgt.p, elen.p);
     if ((rc = un_scan(g, (const uint8_t *)elen.p, w.eoff.p, 8 * nu + 1)) != MCX_OK) return rc;
     HIP_TRY(hipMemcpyAsync(&w.edge_bytes, w.eoff.p + 8 * nu, 8, hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipStreamSynchronize(st));  // before the scratch of this function goes
-  un_clock("ordered and placed", t0);
+  phase_clock("unitigs", "ordered and placed", t0);
   return MCX_OK;
 }
 
@@ -3987,8 +3915,8 @@ extern "C" int mcx_graph_unitigs(mcx_graph *g, int format, uint32_t flags, mcx_s
       const uint64_t lo = std::max(c0, sec[s]), hi = std::min(c1, sec[s + 1]);
       if (lo >= hi) continue;
       uint8_t *dst = (uint8_t *)g->d_stage[b];
-      if (s == 1) UN_LAUNCH(k_un_emit<UnUnits>, (hi - lo + 15) / 16 + 1, uu, lo - sec[1], hi - lo, dst, lo - c0);
-      else if (s == 3) UN_LAUNCH(k_un_emit<UnEdges>, (hi - lo + 15) / 16 + 1, ue, lo - sec[3], hi - lo, dst, lo - c0);
+      if (s == 1) GRID_LAUNCH(k_un_emit<UnUnits>, (hi - lo + 15) / 16 + 1, uu, lo - sec[1], hi - lo, dst, lo - c0);
+      else if (s == 3) GRID_LAUNCH(k_un_emit<UnEdges>, (hi - lo + 15) / 16 + 1, ue, lo - sec[3], hi - lo, dst, lo - c0);
       else {
         const uint64_t from = (s == 0 ? 0 : s == 2 ? pre : pre + mid) + (lo - sec[s]);
         hipLaunchKernelGGL(k_un_text, dim3(1), dim3(64), 0, st, lit, from, hi - lo, dst + (lo - c0));
@@ -4013,7 +3941,7 @@ extern "C" int mcx_graph_unitigs(mcx_graph *g, int format, uint32_t flags, mcx_s
   }
   (void)hipStreamSynchronize(st);  // leave nothing in flight on the staging buffers
   (void)hipStreamSynchronize(g->cstream);
-  un_clock("text emitted and delivered", t0);
+  phase_clock("unitigs", "text emitted and delivered", t0);
   if (rc != MCX_OK) return rc;
   if (stats) { stats->num_unitigs = w.nu; stats->num_kmers = w.n; stats->num_bytes = total; stats->num_cycles = w.ncycles; }
   return MCX_OK;
@@ -4027,19 +3955,17 @@ extern "C" int mcx_graph_unitigs_dev(mcx_graph *g, const mcx_unitigs_arrays *out
   if (rc != MCX_OK) return rc;
   hipStream_t st = g->stream;
   if (w.n) {
-    if (out->keys) UN_LAUNCH_W(k_un_keys, w.n, g->t, w.n, (const uint64_t *)g->clean->slot_of.p, out->keys);
+    if (out->keys) GRID_LAUNCH_W(k_un_keys, w.n, g->t, w.n, (const uint64_t *)g->clean->slot_of.p, out->keys);
     if (out->unitig) HIP_TRY(hipMemcpyAsync(out->unitig, w.kun, w.n * 4, hipMemcpyDeviceToDevice, st));
     if (out->rank) HIP_TRY(hipMemcpyAsync(out->rank, w.krk, w.n * 4, hipMemcpyDeviceToDevice, st));
     if (out->orient) HIP_TRY(hipMemcpyAsync(out->orient, w.kori, w.n, hipMemcpyDeviceToDevice, st));
-    if (out->first) UN_LAUNCH(k_un_first, w.nu, w.nu, (const uint32_t *)w.ufirst.p, out->first);
+    if (out->first) GRID_LAUNCH(k_un_first, w.nu, w.nu, (const uint32_t *)w.ufirst.p, out->first);
     if (out->length) HIP_TRY(hipMemcpyAsync(out->length, w.ulen, w.nu * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
   if (stats) { stats->num_unitigs = w.nu; stats->num_kmers = w.n; stats->num_bytes = 0; stats->num_cycles = w.ncycles; }
   return MCX_OK;
 }
-#undef UN_LAUNCH
-#undef UN_LAUNCH_W
 
 // ---------------------------------------------------------------------------
 // export

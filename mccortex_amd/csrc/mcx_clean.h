@@ -59,15 +59,8 @@ __global__ __launch_bounds__(256) void k_cl_compact(TableView t, uint32_t ncols,
   for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < t.nslots; base += cl_stride()) {
     const uint64_t slot = base + threadIdx.x;
     const bool occ = slot < t.nslots && (key_ptr(t, slot)[0] & kFlag);
-    const unsigned long long act = __builtin_amdgcn_ballot_w64(occ);
-    if (!act) continue;
-    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
-    const uint32_t leader = (uint32_t)__ffsll((long long)act) - 1u;
-    unsigned long long at = 0;
-    if (occ && below == 0) at = atomicAdd(cursor, (unsigned long long)__popcll(act));
-    at = __shfl(at, (int)leader, 64);
+    const uint64_t id = wave_append(cursor, occ);
     if (!occ) continue;
-    const uint64_t id = at + below;
     if (id >= cap) continue;
     slot_of[id] = slot;
     map[slot] = (uint32_t)id;
@@ -237,17 +230,24 @@ __global__ __launch_bounds__(256) void k_cl_decide(uint64_t n, const uint32_t *l
   h.flush(2, hist);
 }
 
+// Which k-mers stay, asked by dense id.  clean and popbubbles keep whole unitigs: a byte per unitig id behind the
+// k-mer's 4-byte unitig id.  (subgraph keeps marked k-mers: KeepMark, mcx_subgraph.h.)
+struct KeepUnitig {
+  const uint32_t *uid;
+  const uint8_t *keep;
+  __device__ __forceinline__ bool operator()(uint64_t id) const { return keep[uid[id]] != 0; }
+};
+
 // prune_edges_to_nodes_lacking_flag: a kept k-mer loses, in every colour, each union edge whose neighbour is
 // not kept -- or is not in the graph at all (the reference asserts there)
-template <int W>
-__global__ __launch_bounds__(256) void k_cl_prune_edges(TableView t, int k, uint32_t ncols, uint64_t n, const uint64_t *slot_of,
-                                                        const uint32_t *map, const uint8_t *ue, const uint32_t *uid,
-                                                        const uint8_t *keep)
+template <int W, class Keep>
+__device__ __forceinline__ void cl_prune_edges(const TableView &t, int k, uint32_t ncols, uint64_t n, const uint64_t *slot_of,
+                                               const uint32_t *map, const uint8_t *ue, Keep keep)
 {
   if (blockIdx.x == 0 && threadIdx.x == 0) table_mark_written(t);
   for (uint64_t i = cl_first(); i < n; i += cl_stride()) {
     const uint32_t e = ue[i];
-    if (!e || !keep[uid[i]]) continue;
+    if (!e || !keep(i)) continue;
     const uint64_t slot = slot_of[i];
     const Kmer<W> key = cl_key<W>(t, slot);
     uint32_t mask = e;
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256) void k_cl_prune_edges(TableView t, int k, uint
       if (!((e >> b) & 1u)) continue;
       uint32_t p = 0;
       const uint64_t s = cl_next<W>(t, key, b >> 2, b & 3u, k, p);
-      if (s == kNoSlot || !keep[uid[map[s]]]) mask &= ~(1u << b);
+      if (s == kNoSlot || !keep(map[s])) mask &= ~(1u << b);
     }
     if (mask == e) continue;
     for (uint32_t c = 0; c < ncols; c++) {
@@ -267,17 +267,32 @@ __global__ __launch_bounds__(256) void k_cl_prune_edges(TableView t, int k, uint
 }
 
 // prune_nodes_lacking_flag_no_edges: the slot becomes a tombstone as in k_intersect_finish
-__global__ __launch_bounds__(256) void k_cl_tombstone(TableView t, uint64_t n, const uint64_t *slot_of, const uint32_t *uid,
-                                                      const uint8_t *keep, Counters *ctr, unsigned long long *removed)
+template <class Keep>
+__device__ __forceinline__ void cl_tombstone(const TableView &t, uint64_t n, const uint64_t *slot_of, Keep keep, Counters *ctr,
+                                             unsigned long long *removed)
 {
   unsigned long long gone = 0;
   for (uint64_t i = cl_first(); i < n; i += cl_stride()) {
-    if (keep[uid[i]]) continue;
+    if (keep(i)) continue;
     key_ptr(t, slot_of[i])[0] = kPending;
     gone++;
   }
   block_add(removed, gone);
   block_add(&ctr->novel, 0ULL - gone);
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void k_cl_prune_edges(TableView t, int k, uint32_t ncols, uint64_t n, const uint64_t *slot_of,
+                                                        const uint32_t *map, const uint8_t *ue, const uint32_t *uid,
+                                                        const uint8_t *keep)
+{
+  cl_prune_edges<W>(t, k, ncols, n, slot_of, map, ue, KeepUnitig{uid, keep});
+}
+
+__global__ __launch_bounds__(256) void k_cl_tombstone(TableView t, uint64_t n, const uint64_t *slot_of, const uint32_t *uid,
+                                                      const uint8_t *keep, Counters *ctr, unsigned long long *removed)
+{
+  cl_tombstone(t, n, slot_of, KeepUnitig{uid, keep}, ctr, removed);
 }
 
 }  // namespace mcx

@@ -91,6 +91,21 @@ __device__ __forceinline__ void table_count_foreign(const TableView &t)
 {
   if (t.touch) table_count_slow(reinterpret_cast<unsigned long long *>(t.touch) - 3);
 }
+// Append behind *cursor (32 or 64 bits, in device memory or LDS): the lanes with `take` set get consecutive indices from
+// ONE atomicAdd per wave, made by the lowest of them and handed round.  Returns this lane's index (nothing where !take).
+// EVERY lane of the wave must reach the call, taking or not: the hand-round reads the lowest taker's register, so a
+// loop around it keeps or drops whole waves (`if (!__builtin_amdgcn_ballot_w64(...)) continue;` in k_sg_seed).
+template <class T> __device__ __forceinline__ uint64_t wave_append(T *cursor, bool take)
+{
+  const unsigned long long act = __builtin_amdgcn_ballot_w64(take);
+  if (!act) return 0;
+  const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
+  const uint32_t leader = (uint32_t)__ffsll((long long)act) - 1u;
+  T at = 0;
+  if (take && below == 0) at = atomicAdd(cursor, (T)__popcll(act));
+  at = __shfl(at, (int)leader, 64);
+  return (uint64_t)at + below;
+}
 // "Hash table is full", fail fast (round 5).  A key whose sub-table is full scans the overflow area linearly, the whole
 // of it (1 / 32 of the table) before it gives up -- and once that area is full EVERY further new key does: a build whose
 // -n is too small for its input (4.8 G distinct k-mers into 1.1 G slots) ground on for a quarter of an hour where the

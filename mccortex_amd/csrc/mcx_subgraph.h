@@ -7,7 +7,8 @@
 //                    (--unitigs: flag the k-mer's unitig instead; k_sg_grab then marks and enqueues whole unitigs)
 //   B. k_sg_expand   one level of a wide frontier, one lane per (entry, edge); the last block to finish advances the queue
 //      k_sg_narrow   one workgroup, many levels of a narrow frontier in one launch
-//   C. k_sg_prune_edges, k_sg_tombstone   clean's prune, with keep = mark bit XOR invert per k-mer
+//   C. k_sg_prune_edges, k_sg_tombstone   clean's prune bodies (cl_prune_edges, cl_tombstone) with keep = mark bit XOR
+//                    invert per k-mer
 // State: the dense ids of k_cl_compact (mcx_clean.h), a mark bitset in 32-bit words, ONE queue of n dense ids and a
 // control block.  A k-mer is enqueued by the lane whose atomicOr found its bit clear, so at most once: n entries
 // cannot overflow, and the frontier of a level is the window queue[head, tail) of that array.
@@ -49,15 +50,9 @@ __device__ __forceinline__ bool sg_mark(uint32_t *mark, uint32_t id)
 // append the ids of the pushing lanes behind *cursor: one reservation per wave (every lane of the wave calls this)
 __device__ __forceinline__ void sg_push(const SgView &s, uint32_t *cursor, bool push, uint32_t id)
 {
-  const unsigned long long act = __builtin_amdgcn_ballot_w64(push);
-  if (!act) return;
-  const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
-  const uint32_t leader = (uint32_t)__ffsll((long long)act) - 1u;
-  uint32_t at = 0;
-  if (push && below == 0) at = atomicAdd(cursor, (uint32_t)__popcll(act));
-  at = __shfl(at, (int)leader, 64);
+  const uint64_t at = wave_append(cursor, push);
   if (!push) return;
-  if ((uint64_t)at + below < s.n) s.queue[at + below] = id;
+  if (at < s.n) s.queue[at] = id;
   else s.ctl[kSgOver] = 1u;
 }
 
@@ -220,49 +215,23 @@ template <int W> __global__ __launch_bounds__(kSgBlock) void k_sg_narrow(TableVi
   if (threadIdx.x < kSgCtlWords && threadIdx.x != kSgOver) s.ctl[threadIdx.x] = c[threadIdx.x];
 }
 
-__device__ __forceinline__ bool sg_keep(const uint32_t *mark, uint64_t id, uint32_t invert)
-{
-  return (((mark[id >> 5] >> (id & 31u)) & 1u) ^ invert) != 0;
-}
+// The prune keeps the marked k-mers, or with `invert` the others.  clean's form (KeepUnitig) reads a byte per unitig
+// behind a 4-byte id per k-mer; serving it an identity uid would cost 5 n bytes of scratch and a pass to unpack the bitset.
+struct KeepMark {
+  const uint32_t *mark;
+  uint32_t invert;
+  __device__ __forceinline__ bool operator()(uint64_t id) const { return (((mark[id >> 5] >> (id & 31u)) & 1u) ^ invert) != 0; }
+};
 
-// k_cl_prune_edges with a keep bit per k-mer: clean's form reads keep[uid[i]], a byte per unitig behind a 4-byte id per
-// k-mer; serving it an identity uid would cost 5 n bytes of scratch and a pass to unpack the bitset
 template <int W>
 __global__ __launch_bounds__(256) void k_sg_prune_edges(TableView t, int k, uint32_t ncols, SgView s, uint32_t invert)
 {
-  if (blockIdx.x == 0 && threadIdx.x == 0) table_mark_written(t);
-  for (uint64_t i = cl_first(); i < s.n; i += cl_stride()) {
-    const uint32_t e = s.ue[i];
-    if (!e || !sg_keep(s.mark, i, invert)) continue;
-    const uint64_t slot = s.slot_of[i];
-    const Kmer<W> key = cl_key<W>(t, slot);
-    uint32_t mask = e;
-    for (uint32_t b = 0; b < 8; b++) {
-      if (!((e >> b) & 1u)) continue;
-      uint32_t p = 0;
-      const uint64_t nb = cl_next<W>(t, key, b >> 2, b & 3u, k, p);
-      if (nb == kNoSlot || !sg_keep(s.mark, s.map[nb], invert)) mask &= ~(1u << b);
-    }
-    if (mask == e) continue;
-    for (uint32_t c = 0; c < ncols; c++) {
-      uint64_t *v = val_ptr(t, slot, c);
-      const uint64_t x = *v;
-      *v = (x & ~0xffULL) | (x & mask);
-    }
-  }
+  cl_prune_edges<W>(t, k, ncols, s.n, s.slot_of, s.map, s.ue, KeepMark{s.mark, invert});
 }
 
-// k_cl_tombstone with the same keep bit
 __global__ __launch_bounds__(256) void k_sg_tombstone(TableView t, SgView s, uint32_t invert, Counters *ctr, unsigned long long *removed)
 {
-  unsigned long long gone = 0;
-  for (uint64_t i = cl_first(); i < s.n; i += cl_stride()) {
-    if (sg_keep(s.mark, i, invert)) continue;
-    key_ptr(t, s.slot_of[i])[0] = kPending;
-    gone++;
-  }
-  block_add(removed, gone);
-  block_add(&ctr->novel, 0ULL - gone);
+  cl_tombstone(t, s.n, s.slot_of, KeepMark{s.mark, invert}, ctr, removed);
 }
 
 }  // namespace mcx
