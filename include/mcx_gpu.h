@@ -431,6 +431,33 @@ int mcx_graph_subgraph_seed_reads(mcx_graph *g, const uint8_t *bases, const uint
 int mcx_graph_subgraph_seed_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes);
 int mcx_graph_subgraph_finish(mcx_graph *g, uint32_t dist, uint32_t flags, mcx_subgraph_stats *stats);
 
+/* `reads` (src/commands/ctx_reads.c; read_touches_graph, with READ_TO_BKMERS and no quality or homopolymer cutoff):
+ * which reads share a k-mer with the graph.  A read touches the graph iff some k-mer of it is a key of the table;
+ * its k-mers are those of every maximal run of ACGTacgt that is at least k long, lower case counts as upper case and
+ * any other byte ends a run; the lookup is by canonical key and colours do not matter.  The answer is a function of
+ * the table's key set and the reads alone, not of the table's size or load, the chunking or the "grid" knob.  The
+ * reference stops at a read's first hit; here every k-mer is looked up (one pass marks a bit per stream position, a
+ * second ORs the bits of each read), so the two k-mer counts are exact.  The table is only read.
+ *   mcx_graph_reads_touch   takes the layout of mcx_graph_add_reads (read r is bases[off[r] .. off[r + 1])) and writes
+ *       hit[r] = 1 or 0.  Flushes pending inserts first.  Synchronous: hit is valid on return.  The reads go through
+ *       the pinned staging buffers as ASCII, in chunks bounded by what a buffer holds ("reads_chunk" of
+ *       mcx_graph_configure lowers the bound: a test knob); a read longer than a chunk goes in pieces that overlap by
+ *       k - 1 bases and its byte is the OR of its pieces'.  stats_accum, if given, is added to.  nreads == 0 is MCX_OK.
+ *   mcx_graph_reads_touch_stream_dev   the same over a stream in HBM: ASCII, 16-byte aligned, read i at positions
+ *       [d_stream_off[i], d_stream_off[i + 1] - 1) with one separator byte (any non-base byte) behind it, so
+ *       d_stream_off holds nreads + 1 64-bit offsets and d_stream_off[nreads] <= nbytes; d_hit takes nreads bytes.
+ *       Asynchronous on the handle's stream; the masks (1 bit per stream position) are kept on the handle.
+ * Refusals (MCX_ERR_ARG): a graph split over devices, a handle in intersect mode. */
+typedef struct {
+  uint64_t num_reads, num_reads_hit;
+  uint64_t num_kmers;        /* k-mer occurrences in the reads, in the graph or not */
+  uint64_t num_kmers_found;  /* occurrences whose k-mer is in the graph */
+} mcx_touch_stats;
+int mcx_graph_reads_touch(mcx_graph *g, const uint8_t *bases, const uint64_t *read_offsets, uint64_t nreads,
+                          uint8_t *hit /* nreads bytes, 0/1 */, mcx_touch_stats *stats_accum /* optional, += */);
+int mcx_graph_reads_touch_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes,
+                                     const void *d_stream_off /* nreads+1 u64 */, uint64_t nreads, void *d_hit);
+
 /* `inferedges`: infer_kmer_edges (src/tools/infer_edges.c) for every record of `recs` (.ctx body
  * layout, ncols == the graph's colours) against the k-mers loaded into the graph.  Each edge that some
  * colour lacks (default, --all) or that some colour has and another lacks (MCX_INFER_POP, --pop)

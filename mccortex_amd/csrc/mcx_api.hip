@@ -33,6 +33,7 @@
 #include "mcx_unitigs.h"
 #include "mcx_pop.h"
 #include "mcx_subgraph.h"
+#include "mcx_reads.h"
 
 using namespace mcx;
 
@@ -272,6 +273,11 @@ struct mcx_graph {
   struct CleanCache *clean = nullptr;     // clean: the unitig decomposition of mcx_graph_unitig_stats (mcx_clean.h)
   struct SubgraphState *subgraph = nullptr;  // subgraph: marks and queue between mcx_graph_subgraph_begin and _finish (mcx_subgraph.h)
   uint32_t subgraph_narrow = 0;           // frontiers of up to this many k-mers go to k_sg_narrow (0: never; off until it is timed)
+  // ---- reads (mcx_reads.h): what mcx_graph_reads_touch* keep between calls ----
+  unsigned long long *d_rt_cnt = nullptr;  // [k-mer occurrences probed, occurrences found] of the current host call
+  uint64_t *d_rt_mask = nullptr;           // hit masks of the device entry, 1 bit per stream position (grows, never shrinks)
+  uint64_t rt_mask_bytes = 0;
+  uint64_t reads_chunk = 0;                // test knob: stream bytes per chunk of mcx_graph_reads_touch (0 = what a staging buffer holds)
 };
 
 // how the kernels that walk records / reads on every shard tell their own keys (mcx_kernels.h: OwnerSpec)
@@ -498,6 +504,8 @@ extern "C" void mcx_graph_destroy(mcx_graph *g)
   if (g->d_ctr) (void)hipFree(g->d_ctr);
   if (g->d_readstrt) (void)hipFree(g->d_readstrt);
   if (g->d_infer) (void)hipFree(g->d_infer);
+  if (g->d_rt_cnt) (void)hipFree(g->d_rt_cnt);
+  if (g->d_rt_mask) (void)hipFree(g->d_rt_mask);
   clean_drop(g);
   subgraph_drop(g);
   if (g->h_ctr) (void)hipHostFree(g->h_ctr);
@@ -1427,6 +1435,7 @@ extern "C" int mcx_graph_configure(mcx_graph *g, const char *key, uint64_t value
     return MCX_OK;
   }
   if (!strcmp(key, "unitigs_chunk")) { g->unitigs_chunk = value; return MCX_OK; }  // test knob: chunk seams anywhere in the text
+  if (!strcmp(key, "reads_chunk")) { g->reads_chunk = value; return MCX_OK; }  // test knob: chunk seams and reads in pieces at small sizes
   if (!strcmp(key, "subgraph_narrow")) { g->subgraph_narrow = (uint32_t)std::min<uint64_t>(value, (uint64_t)kSgBlock); return MCX_OK; }
   if (!strcmp(key, "grid_stream")) { g->grid_stream = (int)value; return MCX_OK; }
   if (!strcmp(key, "grid_split")) { g->grid_split = (int)value; return MCX_OK; }
@@ -3720,6 +3729,143 @@ extern "C" int mcx_graph_subgraph_finish(mcx_graph *g, uint32_t dist, uint32_t f
   subgraph_drop(g);  // (with the dense ids: they described the graph before the prune)
   if (rc == MCX_OK && stats) *stats = out;
   return rc;
+}
+
+// ---------------------------------------------------------------------------
+// reads (ctx_reads.c): which reads share a k-mer with the graph -- mcx_reads.h
+// ---------------------------------------------------------------------------
+static int reads_touch_begin(mcx_graph *g)
+{
+  if (!g) return fail(MCX_ERR_ARG, "null graph");
+  if (g->as_group || g->group || g->t.lbo || g->own_lbo)
+    return fail(MCX_ERR_ARG, "reads needs the whole table on one device, not a graph split over devices (a read's k-mers are on every shard)");
+  if (g->hidden >= 0) return fail(MCX_ERR_ARG, "reads does not take a graph in intersect mode");
+  HIP_TRY(hipSetDevice(g->device));
+  if (!g->d_rt_cnt) {
+    HIP_TRY(hipMalloc((void **)&g->d_rt_cnt, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), g->stream));
+  }
+  return flush_deferred(g);  // the lookups see every insert made so far
+}
+
+// the two passes over one stream of whole reads (positions [0, nbytes)), on the handle's stream
+static int reads_touch_launch(mcx_graph *g, const uint8_t *d_stream, uint64_t nbytes, const uint64_t *d_off, uint64_t nreads, uint64_t *d_mask,
+                              uint8_t *d_hit)
+{
+  hipStream_t st = g->stream;
+  const StreamArgs a = make_args(g, StreamLaunch{d_stream, nbytes, 0, nbytes, nullptr});
+  if (a.ntiles) GRID_LAUNCH_W(k_rt_probe, a.ntiles * (uint64_t)kThreads, a, g->t, reinterpret_cast<uint16_t *>(d_mask), g->d_rt_cnt);
+  GRID_LAUNCH(k_rt_reads, nreads, (const uint64_t *)d_mask, a.ntiles * (uint64_t)kTile, d_off, nreads, g->k, d_hit);
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_reads_touch_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes, const void *d_stream_off, uint64_t nreads,
+                                                void *d_hit)
+{
+  int rc = reads_touch_begin(g);
+  if (rc != MCX_OK) return rc;
+  if (((uintptr_t)d_stream & 15) != 0) return fail(MCX_ERR_ARG, "stream must be 16-byte aligned");
+  if (((uintptr_t)d_stream_off & 7) != 0) return fail(MCX_ERR_ARG, "stream offsets must be 8-byte aligned");
+  if (!nreads) return MCX_OK;
+  if (!d_stream_off || !d_hit || (nbytes && !d_stream)) return fail(MCX_ERR_ARG, "null stream buffers");
+  const uint64_t need = (nbytes + kTile - 1) / kTile * (kTile / 8);
+  if (need > g->rt_mask_bytes) {
+    HIP_TRY(hipStreamSynchronize(g->stream));  // an earlier call may still read the old masks
+    if (g->d_rt_mask) (void)hipFree(g->d_rt_mask);
+    g->d_rt_mask = nullptr;
+    g->rt_mask_bytes = 0;
+    HIP_TRY(hipMalloc((void **)&g->d_rt_mask, need));
+    g->rt_mask_bytes = need;
+  }
+  return reads_touch_launch(g, (const uint8_t *)d_stream, nbytes, (const uint64_t *)d_stream_off, nreads, g->d_rt_mask, (uint8_t *)d_hit);
+}
+
+// Host reads through the pinned staging buffers as ASCII.  A chunk stands alone: whole reads each followed by a
+// separator, or ONE piece of a read that does not fit a chunk, also followed by a separator; consecutive pieces overlap
+// by k - 1 bases, so every k-mer of the read starts in exactly one piece, and the read's byte is the OR of its pieces'.
+// One staging pair holds everything of a chunk: stream, offsets, the hit bytes coming back (pinned on the host side)
+// and, on the device side only, the hit masks.
+extern "C" int mcx_graph_reads_touch(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, uint8_t *hit,
+                                     mcx_touch_stats *stats_accum)
+{
+  int rc = reads_touch_begin(g);
+  if (rc != MCX_OK) return rc;
+  if (nreads && (!off || !hit)) return fail(MCX_ERR_ARG, "null read buffers");
+  if (!nreads) return MCX_OK;
+  if (!bases && off[nreads] != off[0]) return fail(MCX_ERR_ARG, "null read buffers");
+  if ((rc = ensure_stage(g)) != MCX_OK) return rc;
+  // layout: [0, C) stream | offsets (R + 1) | hit bytes R | masks, 512 bytes per tile; R = C / 16 reads at most
+  const uint64_t S = g->stage_alloc;
+  uint64_t C = (std::min<uint64_t>(kStageBytes, g->reads_chunk ? g->reads_chunk : ~0ull) + 63) / 64 * 64;
+  if (S < 704 + 256 * 27 / 16) return fail(MCX_ERR_ARG, "reads: the staging buffers (%llu bytes) are too small", (unsigned long long)S);
+  C = std::max<uint64_t>(256, std::min<uint64_t>(C, ((S - 704) * 16 / 27) & ~63ull));
+  const uint64_t R = C / 16, off_at = C, hit_at = (off_at + 8 * (R + 1) + 15) & ~15ull, mask_at = (hit_at + R + 63) & ~63ull;
+  if (mask_at + (C + kTile - 1) / kTile * (kTile / 8) > S) return fail(MCX_ERR_HIP, "reads: internal error in the staging layout");
+  hipStream_t st = g->stream;
+  HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
+  memset(hit, 0, nreads);
+  struct { uint64_t r0, n; } inflight[mcx_graph::kStageBufs] = {};
+  auto harvest = [&](int b) {  // (after ev[b]: the chunk's bytes have landed)
+    const uint8_t *h = g->h_stage[b] + hit_at;
+    for (uint64_t j = 0; j < inflight[b].n; j++) hit[inflight[b].r0 + j] |= h[j];
+    inflight[b].n = 0;
+  };
+  const uint64_t k1 = (uint64_t)g->k - 1;
+  uint64_t r = 0, r_pos = 0;  // next read, first base of it that the next piece starts with
+  while (r < nreads) {
+    const int b = g->cur;
+    g->cur = (g->cur + 1) % mcx_graph::kStageBufs;
+    HIP_TRY(hipEventSynchronize(g->ev[b]));  // previous use of this buffer finished
+    harvest(b);
+    uint8_t *hs = g->h_stage[b];
+    uint64_t *ho = reinterpret_cast<uint64_t *>(hs + off_at);
+    uint64_t L = 0, n = 0;
+    const uint64_t r0 = r;
+    ho[0] = 0;
+    while (r < nreads && n < R) {
+      const uint64_t len = off[r + 1] - off[r];
+      if (r_pos == 0 && len + 1 <= C - L) {
+        if (len) memcpy(hs + L, bases + off[r], len);
+        L += len;
+        hs[L++] = '\n';
+        ho[++n] = L;
+        r++;
+      } else if (L == 0) {  // a read longer than a chunk: a piece on its own
+        const uint64_t take = std::min(len - r_pos, C - 1);
+        memcpy(hs, bases + off[r] + r_pos, take);
+        L = take;
+        hs[L++] = '\n';
+        ho[++n] = L;
+        if (r_pos + take == len) { r++; r_pos = 0; }
+        else r_pos += take - k1;
+        break;
+      } else {
+        break;
+      }
+    }
+    uint8_t *ds = g->d_stage[b];
+    HIP_TRY(hipMemcpyAsync(ds, hs, L, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ds + off_at, ho, 8 * (n + 1), hipMemcpyHostToDevice, st));
+    rc = reads_touch_launch(g, ds, L, reinterpret_cast<const uint64_t *>(ds + off_at), n, reinterpret_cast<uint64_t *>(ds + mask_at), ds + hit_at);
+    if (rc != MCX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(hs + hit_at, ds + hit_at, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(g->ev[b], st));
+    inflight[b].r0 = r0;
+    inflight[b].n = n;
+  }
+  unsigned long long h[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(h, g->d_rt_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int b = 0; b < mcx_graph::kStageBufs; b++) harvest(b);
+  if (stats_accum) {
+    uint64_t nh = 0;
+    for (uint64_t i = 0; i < nreads; i++) nh += hit[i];
+    stats_accum->num_reads += nreads;
+    stats_accum->num_reads_hit += nh;
+    stats_accum->num_kmers += h[0];
+    stats_accum->num_kmers_found += h[1];
+  }
+  return MCX_OK;
 }
 
 // ---------------------------------------------------------------------------

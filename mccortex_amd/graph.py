@@ -24,6 +24,7 @@ SYMBOLS = [
     "mcx_graph_infer_edges", "mcx_graph_infer_edges_dev", "mcx_graph_unitig_stats", "mcx_graph_clean",
     "mcx_graph_unitigs", "mcx_graph_unitigs_dev", "mcx_graph_pop_bubbles",
     "mcx_graph_subgraph_begin", "mcx_graph_subgraph_seed_reads", "mcx_graph_subgraph_seed_stream_dev", "mcx_graph_subgraph_finish",
+    "mcx_graph_reads_touch", "mcx_graph_reads_touch_stream_dev",
 ]
 
 
@@ -79,6 +80,14 @@ class SubgraphStats(C.Structure):
     """mcx_subgraph_stats"""
     _fields_ = [(n, C.c_uint64) for n in ("num_seed_kmers", "num_seed_found", "nkmers_before", "nkmers_kept", "nkmers_removed")] + \
                [("levels", C.c_uint32), ("narrow_launches", C.c_uint32), ("max_frontier", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class TouchStats(C.Structure):
+    """mcx_touch_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("num_reads", "num_reads_hit", "num_kmers", "num_kmers_found")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -148,6 +157,8 @@ def lib():
     L.mcx_graph_subgraph_seed_reads.argtypes = [vp, vp, vp, C.c_uint64]
     L.mcx_graph_subgraph_seed_stream_dev.argtypes = [vp, vp, C.c_uint64]
     L.mcx_graph_subgraph_finish.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(SubgraphStats)]
+    L.mcx_graph_reads_touch.argtypes = [vp, vp, vp, C.c_uint64, vp, C.POINTER(TouchStats)]
+    L.mcx_graph_reads_touch_stream_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp]
     L.mcx_graph_unitigs.argtypes = [vp, C.c_int, C.c_uint32, SINK_FN, vp, C.POINTER(UnitigsStats)]
     L.mcx_graph_unitigs_dev.argtypes = [vp, C.POINTER(UnitigsArrays), C.POINTER(UnitigsStats)]
     L.mcx_graph_infer_edges.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, u64p]
@@ -513,6 +524,21 @@ class Graph:
         _check(self.L.mcx_graph_subgraph_finish(self.h, int(dist), (SUBGRAPH_UNITIGS if unitigs else 0) | (SUBGRAPH_INVERT if invert else 0),
                                                 C.byref(st)))
         return st.as_dict()
+
+    def reads_touch(self, bases, offsets, stats=None):
+        """`reads` (ctx_reads.c, read_touches_graph): (np.uint8[nreads] of 0 / 1, TouchStats) -- hit[r] = 1 iff read r
+        (bases[offsets[r]:offsets[r + 1]]) has a k-mer in the graph.  `stats`, if given, is added to."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nreads = max(len(offsets) - 1, 0)
+        hit = np.zeros(nreads, dtype=np.uint8)
+        st = stats if stats is not None else TouchStats()
+        _check(self.L.mcx_graph_reads_touch(self.h, _ptr(bases), _ptr(offsets), nreads, _ptr(hit), C.byref(st)))
+        return hit, st
+
+    def reads_touch_stream_dev(self, d_stream, nbytes, d_stream_off, nreads, d_hit):
+        """the same over a stream in HBM (torch tensors or addresses); asynchronous on the graph's stream"""
+        _check(self.L.mcx_graph_reads_touch_stream_dev(self.h, _ptr(d_stream), int(nbytes), _ptr(d_stream_off), int(nreads), _ptr(d_hit)))
 
     def subgraph(self, seeds, dist=0, invert=False, unitigs=False):
         """`subgraph` (ctx_subgraph.c): keep the k-mers within `dist` edges of the k-mers of `seeds` (a list of str or

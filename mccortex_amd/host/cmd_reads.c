@@ -1,0 +1,431 @@
+/* cmd_reads.c -- `mccortex<K> reads` (src/commands/ctx_reads.c): same options, messages and output files.  The graphs
+ * are flattened into colour 0 of a one-colour table in HBM, as `unitigs` loads them; which reads share a k-mer with it
+ * is decided on the MI355X (mcx_graph_reads_touch), batch by batch, while a reader thread parses the next batch.
+ *
+ * Where this differs from the reference (DESIGN.md lists it): the survivors are written in input order (the reference's
+ * workers write in whatever order they finish); read names come from this repository's own parser under the published
+ * rules of the seq_file library; --device picks the GPU. */
+#define _GNU_SOURCE
+#include "host.h"
+
+#include <getopt.h>
+#include <pthread.h>
+#include <stdlib.h>
+#include <string.h>
+#include <strings.h>
+
+#include "../../include/mcx_gpu.h"
+
+#define DEFAULT_MEM (1UL << 29) /* cmd.h:13 */
+#define READS_BATCH_BASES (32UL << 20) /* of build's order: bases per device call */
+
+static const char reads_usage[] =
+"usage: " CMD_NAME " reads [options] <in.ctx>[:cols] [in2.ctx ...]\n"
+"\n"
+"  Filters reads based on which have a kmer in the graph. \n"
+"\n"
+"  -h, --help                  This help message\n"
+"  -q, --quiet                 Silence status output normally printed to STDERR\n"
+"  -f, --force                 Overwrite output files\n"
+"  -m, --memory <mem>          Memory to use\n"
+"  -n, --nkmers <kmers>        Number of hash table entries (e.g. 1G ~ 1 billion)\n"
+"  -t, --threads <T>           Number of threads to use [default: 2]\n"
+"  -F, --format <f>            Output format may be: FASTA, FASTQ [default: FASTQ]\n"
+"  -v, --invert                Print reads/read pairs with no kmer in graph\n"
+"  -1, --seq  <in>:<O>         Writes output to <O>.fq.gz\n"
+"  -2, --seq2 <in1>:<in2>:<O>  Writes output to <O>.{1,2}.fq.gz\n"
+"  -i, --seqi <in>:<O>         Writes output to <O>.{1,2}.fq.gz\n"
+"      --device <N>            GPU to run on [default: 0]\n"
+"\n"
+"  Output is <O>.fq.gz for FASTQ, <O>.fa.gz for FASTA, <O>.txt.gz for plain\n"
+"  Paired reads are saved to e.g. <O>.1.fq.gz, <O>.2.fq.gz, and unpaired reads\n"
+"  to <O>.fq.gz.\n"
+"\n"
+"  User can specify --seq/--seq2/--seqi multiple times. If either read of a\n"
+"  pair touches the graph, both are printed.\n"
+"\n";
+
+enum { OPT_DEVICE = 1000 };
+
+static struct option longopts[] = {
+  {"help", no_argument, NULL, 'h'},         {"force", no_argument, NULL, 'f'},
+  {"memory", required_argument, NULL, 'm'}, {"nkmers", required_argument, NULL, 'n'},
+  {"threads", required_argument, NULL, 't'}, {"format", required_argument, NULL, 'F'},
+  {"invert", no_argument, NULL, 'v'},       {"seq", required_argument, NULL, '1'},
+  {"seq2", required_argument, NULL, '2'},   {"seqi", required_argument, NULL, 'i'},
+  {"device", required_argument, NULL, OPT_DEVICE},
+  {NULL, 0, NULL, 0}};
+
+static void optname(int c, char *out)
+{
+  sprintf(out, "-%c, --Unknown", (char)c);
+  for (int i = 0; longopts[i].name; i++)
+    if (longopts[i].val == c) {
+      if (c < 256) sprintf(out, "-%c, --%s", (char)c, longopts[i].name);
+      else sprintf(out, "--%s", longopts[i].name);
+    }
+}
+
+static void check(int rc, const char *what)
+{
+  if (rc == MCX_ERR_FULL) die("Hash table is full");
+  if (rc != MCX_OK) die("%s: %s", what, mcx_last_error());
+}
+
+/* one --seq / --seq2 / --seqi (AsyncIOInput + AlignReadsData) */
+typedef struct {
+  int kind; /* '1', '2' or 'i' */
+  seq_in *f1, *f2;
+  char *out_base;
+  seq_out *out;
+  size_t printed;
+} reads_task;
+
+/* asyncio_task_parse: <in>:<O> or <in1>:<in2>:<O>, split on ':' or, when there is none, on ',' */
+static void task_parse(reads_task *t, int c, const char *arg)
+{
+  memset(t, 0, sizeof(*t));
+  t->kind = c;
+  char *s = strdup(arg), *paths[4];
+  if (!s) die("Out of memory");
+  const char sep = strchr(s, ':') ? ':' : ',';
+  size_t n = 0;
+  for (char *p = s; n < 4;) {
+    paths[n++] = p;
+    if (!(p = strchr(p, sep))) break;
+    *p++ = '\0';
+  }
+  const bool pe = c == '2';
+  if (n != (pe ? 3u : 2u)) die("Expected -%c %s:<out>", (char)c, pe ? "<in1>:<in2>" : "<in>");
+  t->out_base = paths[pe ? 2 : 1];
+  if (pe) {
+    if (!(t->f1 = seq_in_open(paths[0]))) die("Cannot open %c file: %s", (char)c, paths[0]);
+    if (!(t->f2 = seq_in_open(paths[1]))) die("Cannot open %c file: %s", (char)c, paths[1]);
+  } else if (!(t->f1 = seq_in_open(paths[0]))) {
+    die("Cannot open -%c file: %s", (char)c, paths[0]);
+  }
+  /* (s stays allocated: out_base points into it) */
+}
+
+/* ---- batches on their way from the reader to the device ---- */
+typedef struct {
+  read_batch b;
+  uint8_t *mate; /* [nreads]: 1 = read i and read i + 1 are a pair */
+  size_t task;
+} work;
+
+typedef struct {
+  reads_task *tasks;
+  size_t ntasks;
+  bool want_quals;
+  /* consumer */
+  mcx_graph *g;
+  bool invert;
+  mcx_touch_stats stats;
+  size_t total_reads;
+  uint8_t *hit;
+  size_t cap_hit;
+  /* queue of one batch between the two threads */
+  bool threaded, done;
+  pthread_mutex_t mu;
+  pthread_cond_t cv;
+  work *slot;
+} reads_run;
+
+static work *work_new(reads_run *R, size_t task)
+{
+  work *w = calloc(1, sizeof(*w));
+  if (!w) die("Out of memory");
+  read_batch_init(&w->b, R->want_quals);
+  read_batch_keep_names(&w->b);
+  w->task = task;
+  return w;
+}
+
+static void work_free(work *w)
+{
+  read_batch_free(&w->b);
+  free(w->mate);
+  free(w);
+}
+
+/* filter_reads over one batch: the device says which reads touch the graph, the survivors go out in input order */
+static void process(reads_run *R, work *w)
+{
+  const size_t n = w->b.nreads;
+  reads_task *t = &R->tasks[w->task];
+  if (n > R->cap_hit) {
+    R->cap_hit = n * 2;
+    R->hit = realloc(R->hit, R->cap_hit);
+    if (!R->hit) die("Out of memory");
+  }
+  check(mcx_graph_reads_touch(R->g, w->b.bases, w->b.offsets, n, R->hit, &R->stats), "reads");
+  for (size_t i = 0; i < n; i++) {
+    if (w->mate && w->mate[i]) {
+      if ((R->hit[i] || R->hit[i + 1]) != R->invert) {
+        seq_out_print(t->out, 1, &w->b, i);
+        seq_out_print(t->out, 2, &w->b, i + 1);
+        t->printed += 2;
+      }
+      R->total_reads += 2;
+      i++;
+    } else {
+      if ((R->hit[i] != 0) != R->invert) {
+        seq_out_print(t->out, 0, &w->b, i);
+        t->printed++;
+      }
+      R->total_reads++;
+    }
+  }
+  work_free(w);
+}
+
+static void emit(reads_run *R, work *w)
+{
+  if (!w->b.nreads) { work_free(w); return; }
+  if (!R->threaded) { process(R, w); return; }
+  pthread_mutex_lock(&R->mu);
+  while (R->slot) pthread_cond_wait(&R->cv, &R->mu);
+  R->slot = w;
+  pthread_cond_broadcast(&R->cv);
+  pthread_mutex_unlock(&R->mu);
+}
+
+static void mate_alloc(work *w, size_t n)
+{
+  w->mate = calloc(n ? n : 1, 1);
+  if (!w->mate) die("Out of memory");
+}
+
+static size_t read_len(const read_batch *b, size_t i) { return (size_t)(b->offsets[i + 1] - b->offsets[i]); }
+
+static void keep_tail(read_batch *b, size_t from, bool want_quals)
+{
+  read_batch tmp;
+  read_batch_init(&tmp, want_quals);
+  read_batch_keep_names(&tmp);
+  for (size_t i = from; i < b->nreads; i++) read_batch_append(&tmp, b, i);
+  read_batch_free(b);
+  *b = tmp;
+}
+
+/* the reads of one task, batch by batch, with the pairs marked (asyncio_run_pool's reader side) */
+static void produce_task(reads_run *R, size_t ti)
+{
+  reads_task *t = &R->tasks[ti];
+  if (t->kind == '1') {
+    for (;;) {
+      work *w = work_new(R, ti);
+      seq_in_fill(t->f1, &w->b, READS_BATCH_BASES);
+      if (!w->b.nreads) { work_free(w); break; }
+      emit(R, w);
+    }
+    return;
+  }
+  read_batch b1, b2;
+  read_batch_init(&b1, R->want_quals); read_batch_keep_names(&b1);
+  read_batch_init(&b2, R->want_quals); read_batch_keep_names(&b2);
+  if (t->kind == '2') { /* pair i = read i of each file */
+    for (;;) {
+      const size_t got1 = seq_in_fill(t->f1, &b1, READS_BATCH_BASES), got2 = seq_in_fill(t->f2, &b2, READS_BATCH_BASES);
+      const size_t n = b1.nreads < b2.nreads ? b1.nreads : b2.nreads;
+      if (!got1 && !got2 && n == 0) {
+        if (b1.nreads != b2.nreads) warn("Different number of reads in pe files [%s; %s]", seq_in_path(t->f1), seq_in_path(t->f2));
+        break;
+      }
+      work *w = work_new(R, ti);
+      mate_alloc(w, 2 * n);
+      for (size_t i = 0; i < n; i++) {
+        read_batch_append(&w->b, &b1, i);
+        if (read_len(&b2, i)) { /* (ctx_reads.c:225: a second read without sequence is no read) */
+          w->mate[w->b.nreads - 1] = 1;
+          read_batch_append(&w->b, &b2, i);
+        }
+      }
+      keep_tail(&b1, n, R->want_quals);
+      keep_tail(&b2, n, R->want_quals);
+      emit(R, w);
+    }
+  } else { /* interleaved: two consecutive reads are a pair iff their names say so */
+    for (;;) {
+      const bool eof = seq_in_fill(t->f1, &b1, b1.nbases + READS_BATCH_BASES) == 0;
+      if (!b1.nreads) break;
+      work *w = work_new(R, ti);
+      mate_alloc(w, b1.nreads);
+      size_t i = 0;
+      while (i < b1.nreads) {
+        if (i + 1 == b1.nreads && !eof) break; /* its mate may be the next batch's first read */
+        read_batch_append(&w->b, &b1, i);
+        if (i + 1 < b1.nreads && seq_names_match(b1.names + b1.name_off[i], (size_t)(b1.name_off[i + 1] - b1.name_off[i]),
+                                                 b1.names + b1.name_off[i + 1], (size_t)(b1.name_off[i + 2] - b1.name_off[i + 1]))) {
+          if (read_len(&b1, i + 1)) {
+            w->mate[w->b.nreads - 1] = 1;
+            read_batch_append(&w->b, &b1, i + 1);
+          }
+          i += 2;
+        } else {
+          i++;
+        }
+      }
+      keep_tail(&b1, i, R->want_quals);
+      emit(R, w);
+      if (eof && !b1.nreads) break;
+    }
+  }
+  read_batch_free(&b1);
+  read_batch_free(&b2);
+}
+
+static void *reader_main(void *arg)
+{
+  reads_run *R = arg;
+  for (size_t i = 0; i < R->ntasks; i++) produce_task(R, i);
+  pthread_mutex_lock(&R->mu);
+  R->done = true;
+  pthread_cond_broadcast(&R->cv);
+  pthread_mutex_unlock(&R->mu);
+  return NULL;
+}
+
+int ctx_reads(int argc, char **argv)
+{
+  size_t mem_to_use = DEFAULT_MEM, num_kmers_arg = 0;
+  bool mem_set = false, nkmers_set = false, force = false, invert = false;
+  unsigned nthreads = 0, device = 0;
+  seq_fmt fmt = SEQ_FMT_FASTQ;
+  reads_task *tasks = NULL;
+  size_t ntasks = 0;
+  char cmd[100];
+  int c;
+  optind = 1;
+  while ((c = getopt_long_only(argc, argv, "hfm:n:t:F:v1:2:i:", longopts, NULL)) != -1) {
+    optname(c, cmd);
+    switch (c) {
+      case 'h': print_usage(reads_usage, NULL);
+      case 'f': if (force) print_usage(reads_usage, "%s given twice", cmd); force = true; break;
+      case 't':
+        if (nthreads) print_usage(reads_usage, "%s given twice", cmd);
+        if (!parse_entire_uint(optarg, &nthreads) || !nthreads) print_usage(reads_usage, "%s requires an int x > 0", cmd);
+        break;
+      case 'm':
+        if (mem_set) print_usage(reads_usage, "-m, --memory <M> specifed more than once");
+        if (!mem_to_integer(optarg, &mem_to_use) || !mem_to_use) print_usage(reads_usage, "Invalid memory argument: %s", optarg);
+        mem_set = true; break;
+      case 'n':
+        if (nkmers_set) print_usage(reads_usage, "-n, --nkmers <N> specifed more than once");
+        if (!mem_to_integer(optarg, &num_kmers_arg) || !num_kmers_arg) print_usage(reads_usage, "Invalid hash size: %s", optarg);
+        nkmers_set = true; break;
+      case 'F': /* cmd_check(fmt == SEQ_FMT_FASTQ, cmd): only while the format is still the default */
+        if (fmt != SEQ_FMT_FASTQ) print_usage(reads_usage, "%s given twice", cmd);
+        if (!strcasecmp(optarg, "fq") || !strcasecmp(optarg, "fastq")) fmt = SEQ_FMT_FASTQ;
+        else if (!strcasecmp(optarg, "fa") || !strcasecmp(optarg, "fasta")) fmt = SEQ_FMT_FASTA;
+        else if (!strcasecmp(optarg, "plain") || !strcasecmp(optarg, "txt")) fmt = SEQ_FMT_PLAIN;
+        else print_usage(reads_usage, "Invalid %s {FASTA,FASTQ,PLAIN} option: %s", cmd, optarg);
+        break;
+      case 'v': if (invert) print_usage(reads_usage, "%s given twice", cmd); invert = true; break;
+      case '1': case '2': case 'i':
+        tasks = realloc(tasks, (ntasks + 1) * sizeof(*tasks));
+        if (!tasks) die("Out of memory");
+        task_parse(&tasks[ntasks++], c, optarg);
+        break;
+      case OPT_DEVICE: if (!parse_entire_uint(optarg, &device)) print_usage(reads_usage, "%s requires an int x >= 0: %s", cmd, optarg); break;
+      case ':': case '?': die("`" CMD_NAME " reads -h` for help. Bad option: %s", argv[optind - 1]);
+      default: abort();
+    }
+  }
+  if (nthreads == 0) nthreads = 2;
+  if (ntasks == 0) print_usage(reads_usage, "Please specify at least one sequence file (-1, -2 or -i)");
+  if (optind >= argc) print_usage(reads_usage, "Please specify input graph file(s)");
+
+  /* graph_files_open, then file_filter_flatten(.., 0): every colour of every file goes into colour 0 */
+  const size_t nfiles = (size_t)(argc - optind);
+  ctx_reader *gfiles = calloc(nfiles, sizeof(ctx_reader));
+  if (!gfiles) die("Out of memory");
+  size_t file_ncols = 0, sum_kmers = 0;
+  for (size_t i = 0; i < nfiles; i++) {
+    ctx_reader_open(&gfiles[i], argv[optind + (int)i], file_ncols, MIN_KMER_SIZE, MAX_KMER_SIZE);
+    if (gfiles[i].kmer_size != gfiles[0].kmer_size)
+      print_usage(reads_usage, "Kmer sizes don't match [%u vs %u]", gfiles[0].kmer_size, gfiles[i].kmer_size);
+    if (gfiles[i].into_ncols > file_ncols) file_ncols = gfiles[i].into_ncols;
+    sum_kmers += gfiles[i].num_kmers < 0 ? 0 : (size_t)gfiles[i].num_kmers;
+    for (size_t j = 0; j < gfiles[i].nfilter; j++) gfiles[i].filter[j].into = 0;
+    gfiles[i].into_ncols = 1;
+  }
+  const size_t kmer_size = gfiles[0].kmer_size, W = gfiles[0].num_words;
+
+  /* inputs_attempt_open: every output before anything is loaded; on a failure nothing of this run stays behind */
+  for (size_t i = 0; i < ntasks; i++) {
+    tasks[i].out = seq_out_open(tasks[i].out_base, fmt, tasks[i].kind != '1', force);
+    if (!tasks[i].out) {
+      for (size_t j = 0; j < i; j++) seq_out_close(tasks[j].out, true);
+      die("Error creating output files");
+    }
+  }
+
+  const size_t bits_per_kmer = W * 64; /* sizeof(BinaryKmer) * 8 */
+  table_plan plan;
+  char ebuf[256], s1[64], s2[64];
+  const char *err = table_plan_for_build(mem_to_use, mem_set, num_kmers_arg, nkmers_set, bits_per_kmer, (int64_t)sum_kmers, &plan,
+                                         ebuf, sizeof(ebuf));
+  if (err) {
+    for (size_t j = 0; j < ntasks; j++) seq_out_close(tasks[j].out, true);
+    die("%s", err);
+  }
+  status("[memory] graph: %s", bytes_to_str(plan.bytes, 1, s1));
+
+  if (mcx_device_count() < 1) {
+    for (size_t j = 0; j < ntasks; j++) seq_out_close(tasks[j].out, true);
+    die("No MI355X / HIP device found: %s has no CPU build path", CMD_NAME);
+  }
+  mcx_graph *g = NULL;
+  check(mcx_graph_create(&g, (int)kmer_size, 1, plan.capacity, (int)device), "Cannot allocate graph");
+  for (size_t i = 0; i < nfiles; i++) { ctx_load_graph_file(g, &gfiles[i]); ctx_reader_close(&gfiles[i]); }
+  free(gfiles);
+  uint64_t slots = 0, tbytes = 0;
+  mcx_graph_capacity(g, &slots, &tbytes);
+  status("[hasht] Allocated table in HBM with %s entries, using %s", ulong_to_str(slots, s1), bytes_to_str(tbytes, 1, s2));
+
+  status("Printing reads that do %stouch the graph\n", invert ? "not " : "");
+
+  reads_run R;
+  memset(&R, 0, sizeof(R));
+  R.tasks = tasks; R.ntasks = ntasks;
+  R.want_quals = fmt == SEQ_FMT_FASTQ;
+  R.g = g; R.invert = invert;
+  R.threaded = nthreads > 1;
+  if (R.threaded) { /* the reader fills batch n + 1 while the device decides batch n and its survivors are written */
+    pthread_t th;
+    pthread_mutex_init(&R.mu, NULL);
+    pthread_cond_init(&R.cv, NULL);
+    if (pthread_create(&th, NULL, reader_main, &R) != 0) die("Cannot start the reader thread");
+    for (;;) {
+      pthread_mutex_lock(&R.mu);
+      while (!R.slot && !R.done) pthread_cond_wait(&R.cv, &R.mu);
+      work *w = R.slot;
+      R.slot = NULL;
+      pthread_cond_broadcast(&R.cv);
+      pthread_mutex_unlock(&R.mu);
+      if (!w) break;
+      process(&R, w);
+    }
+    pthread_join(th, NULL);
+    pthread_mutex_destroy(&R.mu);
+    pthread_cond_destroy(&R.cv);
+  } else {
+    for (size_t i = 0; i < ntasks; i++) produce_task(&R, i);
+  }
+  free(R.hit);
+
+  size_t total_printed = 0;
+  for (size_t i = 0; i < ntasks; i++) {
+    total_printed += tasks[i].printed;
+    seq_out_close(tasks[i].out, false);
+    seq_in_close(tasks[i].f1);
+    if (tasks[i].f2) seq_in_close(tasks[i].f2);
+  }
+  free(tasks);
+  status("Total printed %zu / %zu (%.2f%%) reads\n", total_printed, R.total_reads,
+         R.total_reads ? (100.0 * (double)total_printed) / (double)R.total_reads : 0.0);
+  mcx_graph_destroy(g);
+  return EXIT_SUCCESS;
+}

@@ -68,8 +68,17 @@ typedef struct {
   uint64_t *offsets;
   size_t nreads, nbases, cap_bases, cap_reads;
   bool want_quals;
+  /* names, kept only after read_batch_keep_names(): read i is names[name_off[i] .. name_off[i + 1]), the header line
+   * behind '>' or '@' with its comment and without a trailing '\r'; plain input gives empty names */
+  bool want_names;
+  char *names;
+  uint64_t *name_off;
+  size_t names_len, cap_names, cap_name_reads;
 } read_batch;
 void read_batch_init(read_batch *b, bool want_quals);
+void read_batch_keep_names(read_batch *b);
+/* whether two read names belong to mates (seq_read_names_cmp): how --seqi of `reads` pairs consecutive reads */
+bool seq_names_match(const char *a, size_t alen, const char *b, size_t blen);
 void read_batch_clear(read_batch *b);
 void read_batch_free(read_batch *b);
 size_t seq_in_fill(seq_in *s, read_batch *b, size_t max_bases);
@@ -143,6 +152,16 @@ int ctx_clean(int argc, char **argv);       /* src/commands/ctx_clean.c */
 int ctx_pop_bubbles(int argc, char **argv); /* src/commands/ctx_pop_bubbles.c */
 int ctx_subgraph(int argc, char **argv);    /* src/commands/ctx_subgraph.c */
 int ctx_unitigs(int argc, char **argv);     /* src/commands/ctx_unitigs.c */
+int ctx_reads(int argc, char **argv);       /* src/commands/ctx_reads.c */
+
+/* ---- sequence output of `reads` (src/basic/seqout.{h,c}): <O>.fq.gz / .fa.gz / .txt.gz, for a paired task also
+ * <O>.1.* and <O>.2.*; files are created with O_EXCL unless `force`, directories as needed (seq_out.c) ---- */
+typedef struct seq_out seq_out;
+/* NULL on failure, after "Output file already exists: <path>" or "Cannot create file: ..." and with nothing of it left */
+seq_out *seq_out_open(const char *out_base, seq_fmt fmt, bool is_pe, bool force);
+/* read i of the batch into the unpaired file (which = 0) or into <O>.1 / <O>.2 (which = 1 / 2) */
+void seq_out_print(seq_out *o, int which, const read_batch *b, size_t i);
+void seq_out_close(seq_out *o, bool rm); /* rm: delete the files as well */
 /* graph_load: one opened file's colours through its filter into the device table (cmd_clean.c) */
 struct mcx_graph;
 void ctx_load_graph_file(struct mcx_graph *g, ctx_reader *r);

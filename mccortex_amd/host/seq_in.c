@@ -120,6 +120,20 @@ int fq_offset_from_range(int qmin, int qmax)
   return 33;                                        /* unknown: offset 33, max 126 */
 }
 
+/* seq_read_names_cmp of the seq_file library (an empty submodule in the reference checkout: its published rule): two
+ * reads are mates iff their names are equal up to the first whitespace, or equal up to there except for a final '1'
+ * against '2' directly after a '/'.  Two empty names do not match. */
+bool seq_names_match(const char *a, size_t alen, const char *b, size_t blen)
+{
+  size_t na = 0, nb = 0;
+  while (na < alen && a[na] != ' ' && a[na] != '\t' && a[na] != '\n' && a[na] != '\r' && a[na] != '\v' && a[na] != '\f') na++;
+  while (nb < blen && b[nb] != ' ' && b[nb] != '\t' && b[nb] != '\n' && b[nb] != '\r' && b[nb] != '\v' && b[nb] != '\f') nb++;
+  if (na != nb || na == 0) return false;
+  if (memcmp(a, b, na) == 0) return true;
+  if (na < 2 || memcmp(a, b, na - 1) != 0 || a[na - 2] != '/') return false;
+  return (a[na - 1] == '1' && b[nb - 1] == '2') || (a[na - 1] == '2' && b[nb - 1] == '1');
+}
+
 int seq_in_guess_fq_offset(const seq_in *s) { return fq_offset_from_range(s->qmin, s->qmax); }
 
 /* The offset of a file, decided ONCE from the head of the file (the first 1000 records with
@@ -158,9 +172,43 @@ void read_batch_init(read_batch *b, bool want_quals)
   b->offsets[0] = 0;
 }
 
-void read_batch_clear(read_batch *b) { b->nreads = 0; b->nbases = 0; b->offsets[0] = 0; }
+/* opt-in (after read_batch_init): keep the reads' names as a blob + offsets, as the bases are kept */
+void read_batch_keep_names(read_batch *b)
+{
+  b->want_names = true;
+  b->cap_names = 1 << 16; b->cap_name_reads = 1 << 12;
+  b->names = malloc(b->cap_names);
+  b->name_off = malloc((b->cap_name_reads + 1) * sizeof(uint64_t));
+  if (!b->names || !b->name_off) die("Out of memory");
+  b->name_off[0] = 0;
+}
 
-void read_batch_free(read_batch *b) { free(b->bases); free(b->quals); free(b->offsets); memset(b, 0, sizeof(*b)); }
+void read_batch_clear(read_batch *b) { b->nreads = 0; b->nbases = 0; b->offsets[0] = 0; b->names_len = 0; }
+
+void read_batch_free(read_batch *b)
+{
+  free(b->bases); free(b->quals); free(b->offsets); free(b->names); free(b->name_off);
+  memset(b, 0, sizeof(*b));
+}
+
+/* the name of the read that the next batch_end_read() closes */
+static void batch_name(read_batch *b, const char *name, size_t n)
+{
+  if (!b->want_names) return;
+  if (b->nreads + 1 > b->cap_name_reads) {
+    while (b->nreads + 1 > b->cap_name_reads) b->cap_name_reads *= 2;
+    b->name_off = realloc(b->name_off, (b->cap_name_reads + 1) * sizeof(uint64_t));
+    if (!b->name_off) die("Out of memory");
+  }
+  if (b->names_len + n > b->cap_names) {
+    while (b->names_len + n > b->cap_names) b->cap_names *= 2;
+    b->names = realloc(b->names, b->cap_names);
+    if (!b->names) die("Out of memory");
+  }
+  if (n) memcpy(b->names + b->names_len, name, n);
+  b->names_len += n;
+  b->name_off[b->nreads + 1] = b->names_len;
+}
 
 static void batch_reserve(read_batch *b, size_t extra)
 {
@@ -192,6 +240,10 @@ void read_batch_append(read_batch *dst, const read_batch *src, size_t i)
     else memset(dst->quals + dst->nbases, 0, n);
   }
   dst->nbases += n;
+  if (dst->want_names) {
+    if (src->want_names) batch_name(dst, src->names + src->name_off[i], (size_t)(src->name_off[i + 1] - src->name_off[i]));
+    else batch_name(dst, NULL, 0);
+  }
   batch_end_read(dst);
 }
 
@@ -208,6 +260,7 @@ size_t seq_in_fill(seq_in *s, read_batch *b, size_t max_bases)
       memcpy(b->bases + b->nbases, s->line, (size_t)n);
       if (b->want_quals) memset(b->quals + b->nbases, 0, (size_t)n);
       b->nbases += (size_t)n;
+      batch_name(b, NULL, 0);
       batch_end_read(b); added++;
     } else if (s->fmt == SEQ_FMT_FASTA) {
       /* header line */
@@ -215,6 +268,9 @@ size_t seq_in_fill(seq_in *s, read_batch *b, size_t max_bases)
         if ((n = read_line(s)) < 0) break;
         if (n == 0) continue;
         if (s->line[0] != '>') die("Expected '>' in FASTA file %s, got: %.20s", s->path, s->line);
+        batch_name(b, s->line + 1, (size_t)n - 1);
+      } else {
+        batch_name(b, NULL, 0);
       }
       s->pending = -1;
       int c;
@@ -231,6 +287,7 @@ size_t seq_in_fill(seq_in *s, read_batch *b, size_t max_bases)
       if ((n = read_line(s)) < 0) break;
       if (n == 0) continue;
       if (s->line[0] != '@') die("Expected '@' in FASTQ file %s, got: %.20s", s->path, s->line);
+      batch_name(b, s->line + 1, (size_t)n - 1);
       size_t start = b->nbases, slen = 0;
       while ((n = read_line(s)) >= 0 && !(n > 0 && s->line[0] == '+')) {
         batch_reserve(b, (size_t)n);
