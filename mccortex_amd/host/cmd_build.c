@@ -16,7 +16,6 @@
 #include "../../include/mcx_gpu.h"
 
 #define DEFAULT_NTHREADS 2
-#define DEFAULT_MEM (1UL << 29)
 #define IDEAL_OCCUPANCY 0.75f
 #define WARN_OCCUPANCY 0.9f
 #define BATCH_BASES (48u << 20)
@@ -96,13 +95,6 @@ static size_t ngisec = 0;
 
 #define usage_die(...) print_usage(build_usage, __VA_ARGS__)
 
-static void optname(char c, char *out)
-{ /* "-k, --kmer" style, cmd_get_longopt_str (cmd.c:66-84) */
-  sprintf(out, "-%c, --Unknown", c);
-  for (int i = 0; longopts[i].name; i++)
-    if (longopts[i].val == c) sprintf(out, "-%c, --%s", c, longopts[i].name);
-}
-
 /* ctx_build.c:120-131 */
 static void check_sample_name(const char *s)
 {
@@ -135,11 +127,6 @@ static long file_size(const char *path)
   struct stat st;
   if (!strcmp(path, "-") || stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return -1;
   return (long)st.st_size;
-}
-
-static int write_sink(void *ctx, const void *recs, size_t n)
-{
-  return fwrite(recs, 1, n, (FILE *)ctx) == n ? 0 : 1;
 }
 
 /* Sink for a regular output file: every chunk is split over a few threads that pwrite() their part
@@ -187,12 +174,6 @@ static void stage_time(const char *what)
   struct timespec t;
   clock_gettime(CLOCK_MONOTONIC, &t);
   fprintf(stderr, "[timing] %8.1f ms  %s\n", (t.tv_sec - t0.tv_sec) * 1e3 + (t.tv_nsec - t0.tv_nsec) * 1e-6, what);
-}
-
-static void mcx_check(int rc, const char *what)
-{
-  if (rc == MCX_ERR_FULL) die("Hash table is full");
-  if (rc != MCX_OK) die("%s: %s", what, mcx_last_error());
 }
 
 /* one batch of parsed reads -> the GPU (callback of the parallel parser and body of the sequential loop) */
@@ -383,7 +364,7 @@ static void load_task_pcr(mcx_graph *g, build_task *bt)
 static void filter_status(const ctx_reader *r)
 {
   char line[1024];
-  int n = snprintf(line, sizeof(line), "[FileFilter] Reading file %s [%u src colour%s]", r->path, r->num_cols, r->num_cols == 1 ? "" : "s");
+  int n = snprintf(line, sizeof(line), "[FileFilter] Reading file %s [%u src colour%s]", r->path, r->num_cols, plural(r->num_cols));
   bool direct = true;
   for (size_t i = 0; i < r->nfilter; i++) direct &= (r->filter[i].from == i && r->filter[i].into == i);
   if (!direct) {
@@ -393,8 +374,8 @@ static void filter_status(const ctx_reader *r)
   status("%s", line);
 }
 
-/* graph_load (graphs_load.c:86-214) with the hash table on the GPU: merge the header's GraphInfo
- * into the colours it loads into, then stream the records through mcx_graph_add_records */
+/* graph_load as `build` announces it: the file and its filter, then the header's GraphInfo merged into the colours
+ * it loads into, then the records (graph_load of cmd_common.c, with the two coverage warnings) */
 /* isec_col >= 0: the file is an intersection graph, every colour of it goes to that (hidden) colour
  * and its header is not merged (ctx_build.c:347-363); rec_flags: MCX_RECORDS_* */
 static void load_graph_file(mcx_graph *g, ctx_reader *r, col_info *cols, size_t ncols, int isec_col, uint32_t rec_flags)
@@ -410,53 +391,14 @@ static void load_graph_file(mcx_graph *g, ctx_reader *r, col_info *cols, size_t 
   if (isec_col < 0)
     for (size_t i = 0; i < r->nfilter; i++) col_info_merge(&cols[r->filter[i].into], &r->ginfo[r->filter[i].from]);
 
-  const size_t rec_bytes = 8 * (size_t)r->num_words + 5 * (size_t)r->num_cols;
-  const size_t chunk_recs = (64u << 20) / rec_bytes;
-  unsigned char *buf = malloc(chunk_recs * rec_bytes);
-  int32_t *from = malloc(r->nfilter * sizeof(int32_t)), *into = malloc(r->nfilter * sizeof(int32_t));
-  if (!buf || !from || !into) die("Out of memory");
-  for (size_t i = 0; i < r->nfilter; i++) {
-    from[i] = (int32_t)r->filter[i].from;
-    into[i] = isec_col >= 0 ? isec_col : (int32_t)r->filter[i].into;
-  }
-  mcx_records_stats st = {0, 0, 0, -1, -1, -1};
-  bool warned_zero = false, warned_edges = false;
-  for (;;) {
-    const size_t got = fread(buf, 1, chunk_recs * rec_bytes, r->fh);
-    if (got == 0) break;
-    if (got % rec_bytes) {
-      /* graph_file_read_raw: a partial key is "Unexpected end of file", a partial tail an _gfread error */
-      die("Unexpected end of file: %s", r->path);
-    }
-    const uint64_t base = st.nkmers_read;
-    int rc = mcx_graph_add_records(g, buf, got / rec_bytes, (int)r->num_cols, from, into, (int)r->nfilter, rec_flags, &st);
-    if (rc != MCX_OK && st.first_oversized >= 0) die("Oversized kmer in path [kmer: %u]: %s", r->kmer_size, r->path);
-    mcx_check(rc, "load graph records");
-    if (st.first_zero_covg >= 0 && !warned_zero) {
-      char kstr[2 * MAX_KMER_SIZE + 8];
-      kmer_words_to_str(buf + ((uint64_t)st.first_zero_covg - base) * rec_bytes, r->kmer_size, kstr);
-      warn("Kmer has zero covg in all colours [kmer: %s; path: %s]", kstr, r->path);
-      warned_zero = true;
-    }
-    if (st.first_edges_no_covg >= 0 && !warned_edges) {
-      char kstr[2 * MAX_KMER_SIZE + 8];
-      kmer_words_to_str(buf + ((uint64_t)st.first_edges_no_covg - base) * rec_bytes, r->kmer_size, kstr);
-      warn("Kmer has edges but no coverage [kmer: %s; path: %s]", kstr, r->path);
-      warned_edges = true;
-    }
-  }
-  if (r->num_kmers >= 0 && st.nkmers_read != (uint64_t)r->num_kmers)
-    warn("%s kmers in the graph file than expected [exp: %zu; act: %zu; path: %s]",
-         st.nkmers_read > (uint64_t)r->num_kmers ? "More" : "Fewer", (size_t)r->num_kmers, (size_t)st.nkmers_read, r->path);
-  status("[GReader] Loaded %s / %s (%.2f%%) of kmers parsed", ulong_to_str(st.nkmers_loaded, a), ulong_to_str(st.nkmers_read, b),
-         st.nkmers_read ? 100.0 * (double)st.nkmers_loaded / (double)st.nkmers_read : 0.0);
-  free(buf); free(from); free(into);
+  graph_load(g, r, &(graph_load_opts){isec_col, rec_flags, true, NULL, 0});
 }
 
 int ctx_build(int argc, char **argv)
 {
-  size_t nthreads = 0, kmer_size = 0, mem_to_use = DEFAULT_MEM, num_kmers = 0;
-  bool mem_set = false, nkmers_set = false, force = false, sort_kmers = false;
+  size_t nthreads = 0, kmer_size = 0;
+  cmd_mem_args mem = CMD_MEM_ARGS_INIT;
+  bool force = false, sort_kmers = false;
   bool sample_named = false, pref_unused = false, remove_pcr = false;
   uint8_t fq_offset = 0, fq_cutoff = 0, hp_cutoff = 0;
   int intocolour = -1, device = 0, c, matedir = 1 /* FR: build_graph.h:38-42 */;
@@ -466,7 +408,7 @@ int ctx_build(int argc, char **argv)
   /* '+': stop at the first non-option; single-dash long options accepted (cmd.c:87-102, ctx_build.c:149) */
   optind = 1;
   while ((c = getopt_long_only(argc, argv, "+hm:n:t:fk:s:S1:2:i:M:Q:O:H:pPg:I:D:", longopts, NULL)) != -1) {
-    optname((char)c, cmd);
+    cmd_optname(longopts, c, cmd);
     unsigned u;
     switch (c) {
       case 'h': print_usage(build_usage, NULL);
@@ -475,14 +417,8 @@ int ctx_build(int argc, char **argv)
         if (!parse_entire_uint(optarg, &u)) usage_die("%s requires an int x >= 0: %s", cmd, optarg);
         if (!u) usage_die("%s <N> must be > 0: %s", cmd, optarg);
         nthreads = u; break;
-      case 'm':
-        if (mem_set) usage_die("-m, --memory <M> specifed more than once");
-        if (!mem_to_integer(optarg, &mem_to_use) || !mem_to_use) usage_die("Invalid memory argument: %s", optarg);
-        mem_set = true; break;
-      case 'n':
-        if (nkmers_set) usage_die("-n, --nkmers <N> specifed more than once");
-        if (!mem_to_integer(optarg, &num_kmers) || !num_kmers) usage_die("Invalid hash size: %s", optarg);
-        nkmers_set = true; break;
+      case 'm': cmd_mem_set_memory(&mem, build_usage, optarg); break;
+      case 'n': cmd_mem_set_nkmers(&mem, build_usage, optarg); break;
       case 'f': if (force) usage_die("%s given twice", cmd); force = true; break;
       case 'k': {
         if (kmer_size) usage_die("%s given twice", cmd);
@@ -574,7 +510,7 @@ int ctx_build(int argc, char **argv)
   if (optind + 1 > argc) usage_die("Expected exactly one graph file");
   else if (optind + 1 < argc) usage_die("Expected only one graph file. What is this: '%s'", argv[optind]);
   const char *out_path = argv[optind];
-  status("Saving graph to: %s", strcmp(out_path, "-") ? out_path : "STDOUT");
+  status("Saving graph to: %s", outpath(out_path));
   if (nsamples == 0) usage_die("No inputs given");
   if (pref_unused) usage_die("Arguments not given BEFORE sequence file");
   if (!kmer_size) die("kmer size not set with -k <K>");
@@ -632,19 +568,15 @@ int ctx_build(int argc, char **argv)
   /* remove_pcr_dups requires a fw and rv bit per kmer (ctx_build.c:310-315) */
   size_t bits_per_kmer = W * 64 + (4 + 1) * 8 * ncols + (ngisec > 0 ? 8 : 0) + (remove_pcr_used ? 2 : 0) + (sort_kmers ? 64 : 0);
   uint64_t kmers_in_hash = 0;
-  size_t graph_mem = 0;
   char s1[64], s2[64];
   status("[memory] %zu bits per kmer", bits_per_kmer);
   {
     table_plan plan;
-    char ebuf[256];
-    const char *err = table_plan_for_build(mem_to_use, mem_set, num_kmers, nkmers_set, bits_per_kmer,
-                                           max_kmers == SIZE_MAX ? -1 : (int64_t)max_kmers, &plan, ebuf, sizeof(ebuf));
+    const char *err = table_plan_for_args(&mem, bits_per_kmer, max_kmers == SIZE_MAX ? -1 : (int64_t)max_kmers, &plan);
     if (err) die("%s", err);
-    graph_mem = plan.bytes;
     kmers_in_hash = plan.capacity;
+    table_plan_status(&plan);
   }
-  status("[memory] graph: %s", bytes_to_str(graph_mem, 1, s1));
 
   stage_time("arguments parsed");
   if (mcx_device_count() < 1) die("No MI355X / HIP device found: %s has no CPU build path", CMD_NAME);
@@ -674,7 +606,7 @@ int ctx_build(int argc, char **argv)
     fout = fopen(out_path, "wb");
     if (!fout) die("Cannot open output file: %s [%s]", out_path, strerror(errno));
   }
-  status("Writing %zu colour graph to %s\n", ncols, strcmp(out_path, "-") ? out_path : "STDOUT");
+  status("Writing %zu colour graph to %s\n", ncols, outpath(out_path));
 
   mcx_graph *g = NULL;
   if (ndevices == 1) devices[0] = device;
@@ -695,7 +627,7 @@ int ctx_build(int argc, char **argv)
     if (seq_bytes_known && seq_bytes_est + (1u << 20) < window) window = seq_bytes_est + (1u << 20);
     mcx_check(mcx_graph_configure(g, "defer_tuples", window), "flush size");
   }
-  status("[hasht] Allocated table in HBM with %s entries, using %s", ulong_to_str(slots, s1), bytes_to_str(tbytes, 1, s2));
+  hasht_status(g);
   stage_time("table allocated");
 
   col_info *cols = calloc(ncols, sizeof(col_info));
@@ -862,9 +794,7 @@ int ctx_build(int argc, char **argv)
   }
   if (fflush(fout) != 0) die("Cannot write to file");
   stage_time("graph written");
-  const size_t recsz = 8 * W + 5 * ncols;
-  status("Dumped %s kmers in %zu colour%s into: %s (format version: 6; %s)", ulong_to_str(nk, s1), ncols,
-         ncols == 1 ? "" : "s", strcmp(out_path, "-") ? out_path : "STDOUT", bytes_to_str(hdr + nk * recsz, 1, s2));
+  ctx_dumped_status(nk, kmer_size, ncols, hdr, out_path);
   if (fout != stdout) fclose(fout);
   /* The process ends here: the table and the workspace (tens of GB) go back with it.  Releasing
    * them one hipFree at a time first took 0.3 s of a 1.5 s run (MCX_KEEP_DESTROY=1 does it anyway). */

@@ -5,15 +5,12 @@
 #define _GNU_SOURCE
 #include "host.h"
 
-#include <errno.h>
 #include <getopt.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 
 #include "../../include/mcx_gpu.h"
-
-#define DEFAULT_MEM (1UL << 29) /* cmd.h:13 */
 
 static const char clean_usage[] =
 "usage: " CMD_NAME " clean [options] <in.ctx> [in2.ctx ...]\n"
@@ -60,27 +57,6 @@ static struct option longopts[] = {
   {"covg-after", required_argument, NULL, 'C'}, {"device", required_argument, NULL, 'D'},
   {NULL, 0, NULL, 0}};
 
-static void optname(char c, char *out)
-{
-  sprintf(out, "-%c, --Unknown", c);
-  for (int i = 0; longopts[i].name; i++)
-    if (longopts[i].val == c) sprintf(out, "-%c, --%s", c, longopts[i].name);
-}
-
-static void check(int rc, const char *what)
-{
-  if (rc == MCX_ERR_FULL) die("Hash table is full");
-  if (rc != MCX_OK) die("%s: %s", what, mcx_last_error());
-}
-
-static const char *plural(uint64_t n) { return n == 1 ? "" : "s"; }
-static const char *outpath(const char *p) { return strcmp(p, "-") ? p : "STDOUT"; }
-
-static int write_sink(void *ctx, const void *recs, size_t nbytes)
-{
-  return fwrite(recs, 1, nbytes, (FILE *)ctx) == nbytes ? 0 : 1;
-}
-
 /* cleaning_write_covg_histogram / cleaning_write_len_histogram (clean_graph.c) */
 static FILE *open_hist(const char *path, const char *name)
 {
@@ -122,40 +98,14 @@ static void write_len_hist(const char *path, const uint64_t *hist, size_t len, s
   close_hist(f);
 }
 
-/* graph_load (graphs_load.c:86-214): the file's colours through its filter into the table */
-void ctx_load_graph_file(mcx_graph *g, ctx_reader *r)
-{
-  char a[64], b[64];
-  status("[GReader] %s kmers, %s filesize", ulong_to_str((uint64_t)(r->num_kmers < 0 ? 0 : r->num_kmers), a),
-         bytes_to_str((uint64_t)(r->file_size < 0 ? 0 : r->file_size), 1, b));
-  const size_t rec_bytes = 8 * (size_t)r->num_words + 5 * (size_t)r->num_cols;
-  const size_t chunk_recs = (64u << 20) / rec_bytes;
-  unsigned char *buf = malloc(chunk_recs * rec_bytes);
-  int32_t *from = malloc(r->nfilter * sizeof(int32_t)), *into = malloc(r->nfilter * sizeof(int32_t));
-  if (!buf || !from || !into) die("Out of memory");
-  for (size_t i = 0; i < r->nfilter; i++) { from[i] = (int32_t)r->filter[i].from; into[i] = (int32_t)r->filter[i].into; }
-  mcx_records_stats st = {0, 0, 0, -1, -1, -1};
-  for (;;) {
-    const size_t got = fread(buf, 1, chunk_recs * rec_bytes, r->fh);
-    if (got == 0) break;
-    if (got % rec_bytes) die("Unexpected end of file: %s", r->path);
-    int rc = mcx_graph_add_records(g, buf, got / rec_bytes, (int)r->num_cols, from, into, (int)r->nfilter, 0, &st);
-    if (rc != MCX_OK && st.first_oversized >= 0) die("Oversized kmer in path [kmer: %u]: %s", r->kmer_size, r->path);
-    check(rc, "load graph records");
-  }
-  if (r->num_kmers >= 0 && st.nkmers_read != (uint64_t)r->num_kmers)
-    warn("%s kmers in the graph file than expected [exp: %zu; act: %zu; path: %s]",
-         st.nkmers_read > (uint64_t)r->num_kmers ? "More" : "Fewer", (size_t)r->num_kmers, (size_t)st.nkmers_read, r->path);
-  status("[GReader] Loaded %s / %s (%.2f%%) of kmers parsed", ulong_to_str(st.nkmers_loaded, a), ulong_to_str(st.nkmers_read, b),
-         st.nkmers_read ? 100.0 * (double)st.nkmers_loaded / (double)st.nkmers_read : 0.0);
-  free(buf); free(from); free(into);
-}
+/* -x given twice */
+#define ONCE(seen) do { if (seen) print_usage(clean_usage, "%s given twice", cmd); } while (0)
 
 int ctx_clean(int argc, char **argv)
 {
   const char *out_path = NULL;
-  size_t mem_to_use = DEFAULT_MEM, num_kmers_arg = 0;
-  bool mem_set = false, nkmers_set = false, force = false, sort_kmers = false;
+  cmd_mem_args mem = CMD_MEM_ARGS_INIT;
+  bool force = false, sort_kmers = false;
   int min_keep_tip = -1, unitig_min = -1; /* < 0: default, 0: no cleaning */
   bool unitig_cleaning = false, tip_cleaning = false;
   unsigned fallback_thresh = 0, nthreads = 0, user_ncols = 0, device = 0, u = 0;
@@ -164,47 +114,38 @@ int ctx_clean(int argc, char **argv)
   int c;
   optind = 1;
   while ((c = getopt_long_only(argc, argv, "ho:fm:n:t:N:ST::U::B:l:L:c:C:D:", longopts, NULL)) != -1) {
-    optname((char)c, cmd);
+    cmd_optname(longopts, c, cmd);
     switch (c) {
       case 'h': print_usage(clean_usage, NULL);
-      case 'f': if (force) print_usage(clean_usage, "%s given twice", cmd); force = true; break;
-      case 'o': if (out_path) print_usage(clean_usage, NULL); out_path = optarg; break;
-      case 'm':
-        if (mem_set) print_usage(clean_usage, "-m, --memory <M> specifed more than once");
-        if (!mem_to_integer(optarg, &mem_to_use) || !mem_to_use) print_usage(clean_usage, "Invalid memory argument: %s", optarg);
-        mem_set = true; break;
-      case 'n':
-        if (nkmers_set) print_usage(clean_usage, "-n, --nkmers <N> specifed more than once");
-        if (!mem_to_integer(optarg, &num_kmers_arg) || !num_kmers_arg) print_usage(clean_usage, "Invalid hash size: %s", optarg);
-        nkmers_set = true; break;
+      case 'f': ONCE(force); force = true; break;
+      case 'o': if (out_path) print_usage(clean_usage, NULL); out_path = optarg; break; /* (no "given twice" here) */
+      case 'm': cmd_mem_set_memory(&mem, clean_usage, optarg); break;
+      case 'n': cmd_mem_set_nkmers(&mem, clean_usage, optarg); break;
       case 'N':
         if (!parse_entire_uint(optarg, &user_ncols) || !user_ncols) print_usage(clean_usage, "%s requires an int x > 0", cmd);
         break;
-      case 't':
-        if (nthreads) print_usage(clean_usage, "%s given twice", cmd);
-        if (!parse_entire_uint(optarg, &nthreads) || !nthreads) print_usage(clean_usage, "%s requires an int x > 0", cmd);
-        break;
+      case 't': cmd_threads_arg(&nthreads, clean_usage, cmd, optarg); break;
       case 'T':
-        if (min_keep_tip >= 0 || tip_cleaning) print_usage(clean_usage, "%s given twice", cmd);
+        ONCE(min_keep_tip >= 0 || tip_cleaning);
         if (optarg && !parse_entire_uint(optarg, &u)) print_usage(clean_usage, "%s requires an int x >= 0", cmd);
         min_keep_tip = optarg ? (int)u : -1;
         tip_cleaning = true;
         break;
-      case 'S': if (sort_kmers) print_usage(clean_usage, "%s given twice", cmd); sort_kmers = true; break;
+      case 'S': ONCE(sort_kmers); sort_kmers = true; break;
       case 'U':
-        if (unitig_min >= 0 || unitig_cleaning) print_usage(clean_usage, "%s given twice", cmd);
+        ONCE(unitig_min >= 0 || unitig_cleaning);
         if (optarg && !parse_entire_uint(optarg, &u)) print_usage(clean_usage, "%s requires an int x >= 0", cmd);
         unitig_min = optarg ? (int)u : -1;
         unitig_cleaning = true;
         break;
       case 'B':
-        if (fallback_thresh) print_usage(clean_usage, "%s given twice", cmd);
+        ONCE(fallback_thresh);
         if (!parse_entire_uint(optarg, &fallback_thresh) || !fallback_thresh) print_usage(clean_usage, "%s requires an int x > 0", cmd);
         break;
-      case 'l': if (len_before) print_usage(clean_usage, "%s given twice", cmd); len_before = optarg; break;
-      case 'L': if (len_after) print_usage(clean_usage, "%s given twice", cmd); len_after = optarg; break;
-      case 'c': if (covg_before) print_usage(clean_usage, "%s given twice", cmd); covg_before = optarg; break;
-      case 'C': if (covg_after) print_usage(clean_usage, "%s given twice", cmd); covg_after = optarg; break;
+      case 'l': ONCE(len_before); len_before = optarg; break;
+      case 'L': ONCE(len_after); len_after = optarg; break;
+      case 'c': ONCE(covg_before); covg_before = optarg; break;
+      case 'C': ONCE(covg_after); covg_after = optarg; break;
       case 'D': if (!parse_entire_uint(optarg, &device)) print_usage(clean_usage, "%s requires an int x >= 0: %s", cmd, optarg); break;
       case ':': case '?': die("`" CMD_NAME " clean -h` for help. Bad option: %s", argv[optind - 1]);
       default: abort();
@@ -222,30 +163,11 @@ int ctx_clean(int argc, char **argv)
     print_usage(clean_usage, "Output file already exists: %s", out_path);
   if (fallback_thresh && !unitig_cleaning) warn("-B, --fallback <T> without --unitigs");
 
-  /* graph_files_open: each file's colours go after those of the files before it unless its filter says otherwise */
-  const size_t nfiles = (size_t)(argc - optind);
-  ctx_reader *gfiles = calloc(nfiles, sizeof(ctx_reader));
-  if (!gfiles) die("Out of memory");
-  size_t file_ncols = 0, max_kmers = 0, sum_kmers = 0;
-  for (size_t i = 0; i < nfiles; i++) {
-    ctx_reader_open(&gfiles[i], argv[optind + (int)i], file_ncols, MIN_KMER_SIZE, MAX_KMER_SIZE);
-    if (gfiles[i].kmer_size != gfiles[0].kmer_size)
-      print_usage(clean_usage, "Kmer sizes don't match [%u vs %u]", gfiles[0].kmer_size, gfiles[i].kmer_size);
-    if (gfiles[i].into_ncols > file_ncols) file_ncols = gfiles[i].into_ncols;
-    const size_t nk = gfiles[i].num_kmers < 0 ? 0 : (size_t)gfiles[i].num_kmers;
-    if (nk > max_kmers) max_kmers = nk;
-    sum_kmers += nk;
-  }
-  const size_t kmer_size = gfiles[0].kmer_size, W = gfiles[0].num_words;
-
-  /* stats only: flatten every file into one colour */
-  if (out_path == NULL) {
-    file_ncols = 1;
-    for (size_t i = 0; i < nfiles; i++) {
-      for (size_t j = 0; j < gfiles[i].nfilter; j++) gfiles[i].filter[j].into = 0;
-      gfiles[i].into_ncols = 1;
-    }
-  }
+  graph_files in;
+  graph_files_open(argv + optind, (size_t)(argc - optind), clean_usage, &in);
+  const size_t nfiles = in.n, kmer_size = in.files[0].kmer_size, W = in.files[0].num_words;
+  if (out_path == NULL) graph_files_flatten(&in); /* stats only: one colour */
+  size_t file_ncols = in.ncols;
   if (user_ncols && file_ncols < user_ncols) {
     warn("I only need %zu colour%s ('--ncols %u' ignored)", file_ncols, plural(file_ncols), user_ncols);
     user_ncols = (unsigned)file_ncols;
@@ -256,12 +178,12 @@ int ctx_clean(int argc, char **argv)
   if (min_keep_tip < 0) min_keep_tip = 2 * (int)kmer_size;
 
   for (size_t i = 0; i < nfiles; i++) {
-    for (size_t j = 0; j < gfiles[i].nfilter; j++) {
-      const uint32_t from = gfiles[i].filter[j].from;
-      const err_cleaning *cl = &gfiles[i].ginfo[from].cleaning;
+    for (size_t j = 0; j < in.files[i].nfilter; j++) {
+      const uint32_t from = in.files[i].filter[j].from;
+      const err_cleaning *cl = &in.files[i].ginfo[from].cleaning;
       if (cl->cleaned_unitigs && unitig_cleaning)
-        warn("%s:%u already has unitig cleaning with threshold: <%u", gfiles[i].path, from, cl->clean_unitigs_thresh);
-      if (cl->cleaned_tips && tip_cleaning) warn("%s:%u already has had tip cleaned", gfiles[i].path, from);
+        warn("%s:%u already has unitig cleaning with threshold: <%u", in.files[i].path, from, cl->clean_unitigs_thresh);
+      if (cl->cleaned_tips && tip_cleaning) warn("%s:%u already has had tip cleaned", in.files[i].path, from);
     }
   }
 
@@ -280,39 +202,29 @@ int ctx_clean(int argc, char **argv)
   /* ---- memory: as `build --graph` sizes the table for the same inputs ---- */
   const size_t bits_per_kmer = W * 64 + (4 + 1) * 8 * ncols + (sort_kmers ? 64 : 0);
   table_plan plan;
-  char ebuf[256], s1[64], s2[64];
-  const char *err = table_plan_for_build(mem_to_use, mem_set, num_kmers_arg, nkmers_set, bits_per_kmer, (int64_t)sum_kmers,
-                                         &plan, ebuf, sizeof(ebuf));
+  char s1[64];
+  const char *err = table_plan_for_args(&mem, bits_per_kmer, (int64_t)in.sum_kmers, &plan);
   if (err) die("%s", err);
-  status("[cleaning] %zu input graph%s, max kmers: %s, using %zu colour%s", nfiles, plural(nfiles), ulong_to_str(max_kmers, s1),
+  status("[cleaning] %zu input graph%s, max kmers: %s, using %zu colour%s", nfiles, plural(nfiles), ulong_to_str(in.max_kmers, s1),
          ncols, plural(ncols));
-  status("[memory] graph: %s", bytes_to_str(plan.bytes, 1, s1));
-
-  if (mcx_device_count() < 1) die("No MI355X / HIP device found: %s has no CPU build path", CMD_NAME);
+  table_plan_status(&plan);
   mcx_graph *g = NULL;
-  check(mcx_graph_create(&g, (int)kmer_size, (int)ncols, plan.capacity, (int)device), "Cannot allocate graph");
+  if ((err = graph_table_create(&g, &plan, kmer_size, ncols, device))) die("%s", err);
 
-  /* the output header: graph_file_merge_header of every input */
-  col_info *cols = malloc(ncols * sizeof(col_info));
-  if (!cols) die("Out of memory");
-  for (size_t i = 0; i < ncols; i++) col_info_init(&cols[i]);
-  for (size_t i = 0; i < nfiles; i++)
-    for (size_t j = 0; j < gfiles[i].nfilter; j++) col_info_merge(&cols[gfiles[i].filter[j].into], &gfiles[i].ginfo[gfiles[i].filter[j].from]);
-  for (size_t i = 0; i < nfiles; i++) ctx_load_graph_file(g, &gfiles[i]);
+  col_info *cols = graph_files_merge_headers(&in, ncols);
+  for (size_t i = 0; i < nfiles; i++) ctx_load_graph_file(g, &in.files[i]);
 
   uint64_t initial_nkmers = 0;
-  check(mcx_graph_nkmers(g, &initial_nkmers), "nkmers");
+  mcx_check(mcx_graph_nkmers(g, &initial_nkmers), "nkmers");
   status("[cleaning] Total kmers loaded: %s\n", ulong_to_str(initial_nkmers, s1));
-  uint64_t slots = 0, tbytes = 0;
-  mcx_graph_capacity(g, &slots, &tbytes);
-  status("[hasht] Allocated table in HBM with %s entries, using %s", ulong_to_str(slots, s1), bytes_to_str(tbytes, 1, s2));
+  hasht_status(g);
 
   /* ---- cleaning_get_threshold ---- */
   status("[cleaning] Calculating unitig stats with %u threads...", nthreads);
   status("[cleaning]   Using kmer gamma method");
   uint64_t *before = calloc(3 * MCX_CLEAN_NBINS, sizeof(uint64_t)), *after = calloc(3 * MCX_CLEAN_NBINS, sizeof(uint64_t));
   if (!before || !after) die("Out of memory");
-  check(mcx_graph_unitig_stats(g, before), "unitig stats");
+  mcx_check(mcx_graph_unitig_stats(g, before), "unitig stats");
   if (covg_before) write_covg_hist(covg_before, before, before + MCX_CLEAN_NBINS, MCX_CLEAN_NBINS);
   if (len_before) write_len_hist(len_before, before + 2 * MCX_CLEAN_NBINS, MCX_CLEAN_NBINS, kmer_size);
   double alpha = 0, beta = 0, fp = 0, fn = 0;
@@ -343,7 +255,7 @@ int ctx_clean(int argc, char **argv)
       if (min_keep_tip > 0) status("[cleaning] Removing tips shorter than %i...", min_keep_tip);
       status("[cleaning]   using %u threads", nthreads);
       mcx_clean_stats cs;
-      check(mcx_graph_clean(g, (uint32_t)unitig_min, (uint32_t)min_keep_tip, &cs, after), "clean");
+      mcx_check(mcx_graph_clean(g, (uint32_t)unitig_min, (uint32_t)min_keep_tip, &cs, after), "clean");
       char a[50], b[50], c2[50], d[50], e[50], f[50];
       status("[cleaning] Removing %s low coverage unitigs [%s kmer%s], %s unitig tips [%s kmer%s] and %s of both [%s kmer%s]",
              ulong_to_str(cs.num_low_covg_unitigs, a), ulong_to_str(cs.num_low_covg_unitig_kmers, b), plural(cs.num_low_covg_unitig_kmers),
@@ -351,7 +263,7 @@ int ctx_clean(int argc, char **argv)
              ulong_to_str(cs.num_tip_and_low_unitigs, e), ulong_to_str(cs.num_tip_and_low_unitig_kmers, f),
              plural(cs.num_tip_and_low_unitig_kmers));
       uint64_t remain = 0;
-      check(mcx_graph_nkmers(g, &remain), "nkmers");
+      mcx_check(mcx_graph_nkmers(g, &remain), "nkmers");
       status("[cleaning] Remaining kmers: %s removed: %s (%.1f%%)", ulong_to_str(remain, a), ulong_to_str(initial_nkmers - remain, b),
              (100.0 * (double)(initial_nkmers - remain)) / (double)initial_nkmers);
       if (covg_after) write_covg_hist(covg_after, after, after + MCX_CLEAN_NBINS, MCX_CLEAN_NBINS);
@@ -370,26 +282,16 @@ int ctx_clean(int argc, char **argv)
                                                        : (uint32_t)unitig_min;
     }
     uint64_t nk = 0;
-    check(mcx_graph_nkmers(g, &nk), "nkmers");
+    mcx_check(mcx_graph_nkmers(g, &nk), "nkmers");
     char a[100], b[100];
     status("Removed %s of %s (%.2f%%) kmers", ulong_to_str(initial_nkmers - nk, a), ulong_to_str(initial_nkmers, b),
            (100.0 * (double)(initial_nkmers - nk)) / (double)initial_nkmers);
-    FILE *fout = stdout;
-    if (strcmp(out_path, "-") != 0) {
-      fout = fopen(out_path, "wb");
-      if (!fout) die("Cannot open output file: %s [%s]", out_path, strerror(errno));
-    }
-    const size_t hdr = ctx_write_header(fout, (uint32_t)kmer_size, (uint32_t)ncols, cols);
-    check(mcx_graph_export(g, sort_kmers ? 1 : 0, write_sink, fout), "export");
-    if (fflush(fout) != 0) die("Cannot write to file: %s", out_path);
-    status("Dumped %s kmers in %zu colour%s into: %s (format version: 6; %s)", ulong_to_str(nk, a), ncols, plural(ncols),
-           outpath(out_path), bytes_to_str(hdr + nk * (8 * W + 5 * ncols), 1, b));
-    if (fout != stdout && fclose(fout) != 0) die("Cannot write to file: %s", out_path);
+    ctx_write_graph(g, out_path, kmer_size, ncols, cols, sort_kmers);
   }
 
-  for (size_t i = 0; i < ncols; i++) col_info_free(&cols[i]);
-  for (size_t i = 0; i < nfiles; i++) ctx_reader_close(&gfiles[i]);
-  free(cols); free(gfiles); free(before); free(after);
+  col_infos_free(cols, ncols);
+  graph_files_close(&in);
+  free(before); free(after);
   mcx_graph_destroy(g);
   return EXIT_SUCCESS;
 }

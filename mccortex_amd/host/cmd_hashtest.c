@@ -13,7 +13,7 @@
 
 #include "../../include/mcx_gpu.h"
 
-#define DEFAULT_MEM (1UL << 30)   /* cmd.h:12: -m default 1GB */
+#define HASHTEST_MEM (1UL << 30)  /* cmd.h:12: -m default 1GB */
 #define DEFAULT_NTHREADS 2        /* cmd.h:9 */
 
 static const char hashtest_usage[] =
@@ -35,12 +35,12 @@ static struct option hashtest_opts[] = {
   {"kmer", required_argument, NULL, 'k'},    {"func-only", no_argument, NULL, 'F'},
   {"device", required_argument, NULL, 'D'},  {NULL, 0, NULL, 0}};
 
-static void optname(char c, char *out)
+/* this command names an option that takes a value with " <arg>" behind it */
+static void hashtest_opt_str(int c, char *out)
 {
-  sprintf(out, "-%c, --Unknown", c);
+  cmd_optname(hashtest_opts, c, out);
   for (int i = 0; hashtest_opts[i].name; i++)
-    if (hashtest_opts[i].val == c)
-      sprintf(out, "-%c, --%s%s", c, hashtest_opts[i].name, hashtest_opts[i].has_arg == required_argument ? " <arg>" : "");
+    if (hashtest_opts[i].val == c && hashtest_opts[i].has_arg == required_argument) strcat(out, " <arg>");
 }
 
 /* hash_table_print_stats_brief (hash_table.c:301-319) for the table in HBM: its slots and the bytes they take */
@@ -58,29 +58,24 @@ static void print_table_stats(mcx_graph *g)
 
 int ctx_hashtest(int argc, char **argv)
 {
-  size_t nthreads = 0, kmer_size = 0, mem_to_use = DEFAULT_MEM, num_kmers = 0, num_ops = 0;
-  bool threads_set = false, mem_set = false, nkmers_set = false, store_kmers = true;
+  size_t nthreads = 0, kmer_size = 0, num_ops = 0;
+  cmd_mem_args mem = {HASHTEST_MEM, 0, false, false};
+  bool threads_set = false, store_kmers = true;
   unsigned device = 0, u;
   char cmd[100];
   int c;
   if (argc == 1) print_usage(hashtest_usage, NULL); /* "Type a command with no arguments to see help" (mccortex.c) */
   optind = 1;
   while ((c = getopt_long_only(argc, argv, "hm:n:t:k:FD:", hashtest_opts, NULL)) != -1) {
-    optname((char)c, cmd);
+    hashtest_opt_str(c, cmd);
     switch (c) {
       case 'h': print_usage(hashtest_usage, NULL);
       case 't':
         if (threads_set) print_usage(hashtest_usage, "%s given twice", cmd);
         if (!parse_entire_uint(optarg, &u)) print_usage(hashtest_usage, "%s requires an int x >= 0: %s", cmd, optarg);
         nthreads = u; threads_set = true; break;
-      case 'm':
-        if (mem_set) print_usage(hashtest_usage, "-m, --memory <M> specifed more than once");
-        if (!mem_to_integer(optarg, &mem_to_use) || !mem_to_use) print_usage(hashtest_usage, "Invalid memory argument: %s", optarg);
-        mem_set = true; break;
-      case 'n':
-        if (nkmers_set) print_usage(hashtest_usage, "-n, --nkmers <N> specifed more than once");
-        if (!mem_to_integer(optarg, &num_kmers) || !num_kmers) print_usage(hashtest_usage, "Invalid hash size: %s", optarg);
-        nkmers_set = true; break;
+      case 'm': cmd_mem_set_memory(&mem, hashtest_usage, optarg); break;
+      case 'n': cmd_mem_set_nkmers(&mem, hashtest_usage, optarg); break;
       case 'k':
         if (kmer_size) print_usage(hashtest_usage, "%s given twice", cmd);
         if (!parse_entire_uint(optarg, &u) || !u) print_usage(hashtest_usage, "%s requires an int x > 0: %s", cmd, optarg);
@@ -108,11 +103,9 @@ int ctx_hashtest(int argc, char **argv)
     /* every operation adds a (probably unique) kmer: min and max number of kmers are both num_ops */
     const size_t W = (2 * kmer_size + 63) / 64, bits_per_kmer = W * 64;
     table_plan plan;
-    char ebuf[256];
-    const char *err = table_plan_for_build(mem_to_use, mem_set, num_kmers, nkmers_set, bits_per_kmer, (int64_t)num_ops,
-                                           &plan, ebuf, sizeof(ebuf));
+    const char *err = table_plan_for_args(&mem, bits_per_kmer, (int64_t)num_ops, &plan);
     if (err) die("%s", err);
-    status("[memory] graph: %s", bytes_to_str(plan.bytes, 1, s1));
+    table_plan_status(&plan);
     uint64_t hbm_free = 0, hbm_total = 0;
     if (mcx_device_memory((int)device, &hbm_free, &hbm_total) != MCX_OK) die("device query: %s", mcx_last_error());
     const uint64_t dev_bytes = (plan.capacity + plan.capacity / 32) * 8 * (W + 1);
@@ -122,7 +115,7 @@ int ctx_hashtest(int argc, char **argv)
     print_table_stats(g);
   }
 
-  status("[threads] using %zu thread%s (%s-threaded code)", nthreads, nthreads == 1 ? "" : "s", single_threaded ? "single" : "multi");
+  status("[threads] using %zu thread%s (%s-threaded code)", nthreads, plural(nthreads), single_threaded ? "single" : "multi");
 
   struct timeval t0, t1;
   gettimeofday(&t0, NULL);

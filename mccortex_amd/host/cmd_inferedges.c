@@ -17,7 +17,6 @@
 
 #include "../../include/mcx_gpu.h"
 
-#define DEFAULT_MEM (1UL << 29) /* cmd.h:13 */
 #define CHUNK_BYTES (64u << 20)  /* host records per read */
 
 static const char inferedges_usage[] =
@@ -46,19 +45,6 @@ static struct option longopts[] = {
   {"nkmers", required_argument, NULL, 'n'},  {"threads", required_argument, NULL, 't'},
   {"pop", no_argument, NULL, 'P'},           {"all", no_argument, NULL, 'A'},
   {"device", required_argument, NULL, 'D'},  {NULL, 0, NULL, 0}};
-
-static void optname(char c, char *out)
-{
-  sprintf(out, "-%c, --Unknown", c);
-  for (int i = 0; longopts[i].name; i++)
-    if (longopts[i].val == c) sprintf(out, "-%c, --%s", c, longopts[i].name);
-}
-
-static void check(int rc, const char *what)
-{
-  if (rc == MCX_ERR_FULL) die("Hash table is full");
-  if (rc != MCX_OK) die("%s: %s", what, mcx_last_error());
-}
 
 /* futil_fopen_create (file_util.c:139-174): "-" is stdout */
 static FILE *fopen_create(const char *path, bool force)
@@ -96,56 +82,24 @@ static int membuf_sink(void *ctx, const void *recs, size_t nbytes)
   return 0;
 }
 
-/* graph_load (graphs_load.c:86-214) of every colour into the same colour of the table */
-static void load_graph(mcx_graph *g, ctx_reader *r, unsigned char *buf, size_t chunk_recs, size_t rec_bytes)
-{
-  int32_t *cols = malloc(r->num_cols * sizeof(int32_t));
-  if (!cols) die("Out of memory");
-  for (uint32_t c = 0; c < r->num_cols; c++) cols[c] = (int32_t)c;
-  mcx_records_stats st = {0, 0, 0, -1, -1, -1};
-  for (;;) {
-    const size_t got = fread(buf, 1, chunk_recs * rec_bytes, r->fh);
-    if (got == 0) break;
-    if (got % rec_bytes) die("Unexpected end of file: %s", r->path);
-    int rc = mcx_graph_add_records(g, buf, got / rec_bytes, (int)r->num_cols, cols, cols, (int)r->num_cols, 0, &st);
-    if (rc != MCX_OK && st.first_oversized >= 0) die("Oversized kmer in path [kmer: %u]: %s", r->kmer_size, r->path);
-    check(rc, "load graph records");
-  }
-  free(cols);
-  if (r->num_kmers >= 0 && st.nkmers_read != (uint64_t)r->num_kmers)
-    warn("%s kmers in the graph file than expected [exp: %zu; act: %zu; path: %s]",
-         st.nkmers_read > (uint64_t)r->num_kmers ? "More" : "Fewer", (size_t)r->num_kmers, (size_t)st.nkmers_read, r->path);
-  char n0[50], n1[50];
-  status("[GReader] Loaded %s / %s (%.2f%%) of kmers parsed", ulong_to_str(st.nkmers_loaded, n0),
-         ulong_to_str(st.nkmers_read, n1), st.nkmers_read ? 100.0 * (double)st.nkmers_loaded / (double)st.nkmers_read : 0.0);
-}
-
 int ctx_infer_edges(int argc, char **argv)
 {
   const char *out_path = NULL;
-  size_t mem_to_use = DEFAULT_MEM, num_kmers_arg = 0;
-  bool mem_set = false, nkmers_set = false, force = false, add_pop_edges = false, add_all_edges = false;
+  cmd_mem_args mem = CMD_MEM_ARGS_INIT;
+  bool force = false, add_pop_edges = false, add_all_edges = false;
   unsigned device = 0, nthreads = 0;
   char cmd[100];
   int c;
   optind = 1;
   while ((c = getopt_long_only(argc, argv, "hfo:m:n:t:PAD:", longopts, NULL)) != -1) {
-    optname((char)c, cmd);
+    cmd_optname(longopts, c, cmd);
     switch (c) {
       case 'h': print_usage(inferedges_usage, NULL);
       case 'f': if (force) print_usage(inferedges_usage, "%s given twice", cmd); force = true; break;
       case 'o': if (out_path) print_usage(inferedges_usage, "%s given twice", cmd); out_path = optarg; break;
-      case 't':
-        if (!parse_entire_uint(optarg, &nthreads) || !nthreads) print_usage(inferedges_usage, "%s requires an int x > 0", cmd);
-        break;
-      case 'm':
-        if (mem_set) print_usage(inferedges_usage, "-m, --memory <M> specifed more than once");
-        if (!mem_to_integer(optarg, &mem_to_use) || !mem_to_use) print_usage(inferedges_usage, "Invalid memory argument: %s", optarg);
-        mem_set = true; break;
-      case 'n':
-        if (nkmers_set) print_usage(inferedges_usage, "-n, --nkmers <N> specifed more than once");
-        if (!mem_to_integer(optarg, &num_kmers_arg) || !num_kmers_arg) print_usage(inferedges_usage, "Invalid hash size: %s", optarg);
-        nkmers_set = true; break;
+      case 't': nthreads = 0; cmd_threads_arg(&nthreads, inferedges_usage, cmd, optarg); break; /* (may be repeated) */
+      case 'm': cmd_mem_set_memory(&mem, inferedges_usage, optarg); break;
+      case 'n': cmd_mem_set_nkmers(&mem, inferedges_usage, optarg); break;
       case 'A': add_all_edges = true; break;
       case 'P': add_pop_edges = true; break;
       case 'D': if (!parse_entire_uint(optarg, &device)) print_usage(inferedges_usage, "%s requires an int x >= 0: %s", cmd, optarg); break;
@@ -185,23 +139,21 @@ int ctx_infer_edges(int argc, char **argv)
   const size_t ncols = r.num_cols, W = r.num_words;
   const size_t bits_per_kmer = 64 * W + (reading_stream ? ncols * 8 * (4 + 1) : ncols);
   table_plan plan;
-  char ebuf[256], s1[64];
-  const char *err = table_plan_for_build(mem_to_use, mem_set, num_kmers_arg, nkmers_set, bits_per_kmer, r.num_kmers, &plan, ebuf, sizeof(ebuf));
+  const char *err = table_plan_for_args(&mem, bits_per_kmer, r.num_kmers, &plan);
   if (err) die("%s", err);
   status("[memory] %zu bits per kmer", bits_per_kmer);
-  status("[memory] graph: %s", bytes_to_str(plan.bytes, 1, s1));
-
-  if (mcx_device_count() < 1) die("No MI355X / HIP device found: %s has no CPU build path", CMD_NAME);
+  table_plan_status(&plan);
   mcx_graph *g = NULL;
-  check(mcx_graph_create(&g, (int)r.kmer_size, (int)ncols, plan.capacity, (int)device), "Cannot allocate graph");
+  if ((err = graph_table_create(&g, &plan, r.kmer_size, ncols, device))) die("%s", err);
 
   const size_t rec_bytes = 8 * W + 5 * ncols;
   const size_t chunk_recs = CHUNK_BYTES / rec_bytes > 0 ? CHUNK_BYTES / rec_bytes : 1;
   unsigned char *buf = malloc(chunk_recs * rec_bytes);
   if (!buf) die("Out of memory");
-  load_graph(g, &r, buf, chunk_recs, rec_bytes);
+  /* (the path holds no filter: every colour goes into the same colour of the table) */
+  graph_load(g, &r, &(graph_load_opts){-1, 0, false, buf, chunk_recs * rec_bytes});
   uint64_t nkmers = 0;
-  check(mcx_graph_nkmers(g, &nkmers), "nkmers");
+  mcx_check(mcx_graph_nkmers(g, &nkmers), "nkmers");
 
   if (add_pop_edges) status("Inferring edges from population...\n");
   else status("Inferring all missing edges...\n");
@@ -212,8 +164,8 @@ int ctx_infer_edges(int argc, char **argv)
     /* infer_edges over the merged table, then the table after the header as read */
     status("[inferedges] Processing stream");
     membuf m = {NULL, 0, 0};
-    check(mcx_graph_export(g, 0, membuf_sink, &m), "export");
-    check(mcx_graph_infer_edges(g, m.p, m.n / rec_bytes, (int)ncols, flags, &num_kmers_edited), "inferedges");
+    mcx_check(mcx_graph_export(g, 0, membuf_sink, &m), "export");
+    mcx_check(mcx_graph_infer_edges(g, m.p, m.n / rec_bytes, (int)ncols, flags, &num_kmers_edited), "inferedges");
     ctx_write_header_raw(fout, &r);
     write_all(fout, m.p, m.n);
     free(m.p);
@@ -225,7 +177,7 @@ int ctx_infer_edges(int argc, char **argv)
     for (uint64_t left = (uint64_t)r.num_kmers; left > 0;) {
       const size_t n = left < chunk_recs ? (size_t)left : chunk_recs;
       if (fread(buf, 1, n * rec_bytes, r.fh) != n * rec_bytes) die("Unexpected end of file: %s", r.path);
-      check(mcx_graph_infer_edges(g, buf, n, (int)ncols, flags, &nmod), "inferedges");
+      mcx_check(mcx_graph_infer_edges(g, buf, n, (int)ncols, flags, &nmod), "inferedges");
       if (nmod && pwrite(fileno(r.fh), buf, n * rec_bytes, pos) != (ssize_t)(n * rec_bytes))
         die("Cannot write to file: %s [%s]", r.path, strerror(errno));
       num_kmers_edited += nmod;
@@ -241,7 +193,7 @@ int ctx_infer_edges(int argc, char **argv)
       const size_t got = fread(buf, 1, chunk_recs * rec_bytes, r.fh);
       if (got == 0) break;
       const size_t n = got / rec_bytes;
-      check(mcx_graph_infer_edges(g, buf, n, (int)ncols, flags, &nmod), "inferedges");
+      mcx_check(mcx_graph_infer_edges(g, buf, n, (int)ncols, flags, &nmod), "inferedges");
       write_all(fout, buf, n * rec_bytes);
       num_kmers_edited += nmod;
     }

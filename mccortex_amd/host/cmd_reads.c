@@ -16,7 +16,6 @@
 
 #include "../../include/mcx_gpu.h"
 
-#define DEFAULT_MEM (1UL << 29) /* cmd.h:13 */
 #define READS_BATCH_BASES (32UL << 20) /* of build's order: bases per device call */
 
 static const char reads_usage[] =
@@ -56,21 +55,8 @@ static struct option longopts[] = {
   {"device", required_argument, NULL, OPT_DEVICE},
   {NULL, 0, NULL, 0}};
 
-static void optname(int c, char *out)
-{
-  sprintf(out, "-%c, --Unknown", (char)c);
-  for (int i = 0; longopts[i].name; i++)
-    if (longopts[i].val == c) {
-      if (c < 256) sprintf(out, "-%c, --%s", (char)c, longopts[i].name);
-      else sprintf(out, "--%s", longopts[i].name);
-    }
-}
-
-static void check(int rc, const char *what)
-{
-  if (rc == MCX_ERR_FULL) die("Hash table is full");
-  if (rc != MCX_OK) die("%s: %s", what, mcx_last_error());
-}
+/* -x given twice */
+#define ONCE(seen) do { if (seen) print_usage(reads_usage, "%s given twice", cmd); } while (0)
 
 /* one --seq / --seq2 / --seqi (AsyncIOInput + AlignReadsData) */
 typedef struct {
@@ -159,7 +145,7 @@ static void process(reads_run *R, work *w)
     R->hit = realloc(R->hit, R->cap_hit);
     if (!R->hit) die("Out of memory");
   }
-  check(mcx_graph_reads_touch(R->g, w->b.bases, w->b.offsets, n, R->hit, &R->stats), "reads");
+  mcx_check(mcx_graph_reads_touch(R->g, w->b.bases, w->b.offsets, n, R->hit, &R->stats), "reads");
   for (size_t i = 0; i < n; i++) {
     if (w->mate && w->mate[i]) {
       if ((R->hit[i] || R->hit[i + 1]) != R->invert) {
@@ -289,8 +275,8 @@ static void *reader_main(void *arg)
 
 int ctx_reads(int argc, char **argv)
 {
-  size_t mem_to_use = DEFAULT_MEM, num_kmers_arg = 0;
-  bool mem_set = false, nkmers_set = false, force = false, invert = false;
+  cmd_mem_args mem = CMD_MEM_ARGS_INIT;
+  bool force = false, invert = false;
   unsigned nthreads = 0, device = 0;
   seq_fmt fmt = SEQ_FMT_FASTQ;
   reads_task *tasks = NULL;
@@ -299,30 +285,21 @@ int ctx_reads(int argc, char **argv)
   int c;
   optind = 1;
   while ((c = getopt_long_only(argc, argv, "hfm:n:t:F:v1:2:i:", longopts, NULL)) != -1) {
-    optname(c, cmd);
+    cmd_optname(longopts, c, cmd);
     switch (c) {
       case 'h': print_usage(reads_usage, NULL);
-      case 'f': if (force) print_usage(reads_usage, "%s given twice", cmd); force = true; break;
-      case 't':
-        if (nthreads) print_usage(reads_usage, "%s given twice", cmd);
-        if (!parse_entire_uint(optarg, &nthreads) || !nthreads) print_usage(reads_usage, "%s requires an int x > 0", cmd);
-        break;
-      case 'm':
-        if (mem_set) print_usage(reads_usage, "-m, --memory <M> specifed more than once");
-        if (!mem_to_integer(optarg, &mem_to_use) || !mem_to_use) print_usage(reads_usage, "Invalid memory argument: %s", optarg);
-        mem_set = true; break;
-      case 'n':
-        if (nkmers_set) print_usage(reads_usage, "-n, --nkmers <N> specifed more than once");
-        if (!mem_to_integer(optarg, &num_kmers_arg) || !num_kmers_arg) print_usage(reads_usage, "Invalid hash size: %s", optarg);
-        nkmers_set = true; break;
+      case 'f': ONCE(force); force = true; break;
+      case 't': cmd_threads_arg(&nthreads, reads_usage, cmd, optarg); break;
+      case 'm': cmd_mem_set_memory(&mem, reads_usage, optarg); break;
+      case 'n': cmd_mem_set_nkmers(&mem, reads_usage, optarg); break;
       case 'F': /* cmd_check(fmt == SEQ_FMT_FASTQ, cmd): only while the format is still the default */
-        if (fmt != SEQ_FMT_FASTQ) print_usage(reads_usage, "%s given twice", cmd);
+        ONCE(fmt != SEQ_FMT_FASTQ);
         if (!strcasecmp(optarg, "fq") || !strcasecmp(optarg, "fastq")) fmt = SEQ_FMT_FASTQ;
         else if (!strcasecmp(optarg, "fa") || !strcasecmp(optarg, "fasta")) fmt = SEQ_FMT_FASTA;
         else if (!strcasecmp(optarg, "plain") || !strcasecmp(optarg, "txt")) fmt = SEQ_FMT_PLAIN;
         else print_usage(reads_usage, "Invalid %s {FASTA,FASTQ,PLAIN} option: %s", cmd, optarg);
         break;
-      case 'v': if (invert) print_usage(reads_usage, "%s given twice", cmd); invert = true; break;
+      case 'v': ONCE(invert); invert = true; break;
       case '1': case '2': case 'i':
         tasks = realloc(tasks, (ntasks + 1) * sizeof(*tasks));
         if (!tasks) die("Out of memory");
@@ -338,20 +315,10 @@ int ctx_reads(int argc, char **argv)
   if (optind >= argc) print_usage(reads_usage, "Please specify input graph file(s)");
 
   /* graph_files_open, then file_filter_flatten(.., 0): every colour of every file goes into colour 0 */
-  const size_t nfiles = (size_t)(argc - optind);
-  ctx_reader *gfiles = calloc(nfiles, sizeof(ctx_reader));
-  if (!gfiles) die("Out of memory");
-  size_t file_ncols = 0, sum_kmers = 0;
-  for (size_t i = 0; i < nfiles; i++) {
-    ctx_reader_open(&gfiles[i], argv[optind + (int)i], file_ncols, MIN_KMER_SIZE, MAX_KMER_SIZE);
-    if (gfiles[i].kmer_size != gfiles[0].kmer_size)
-      print_usage(reads_usage, "Kmer sizes don't match [%u vs %u]", gfiles[0].kmer_size, gfiles[i].kmer_size);
-    if (gfiles[i].into_ncols > file_ncols) file_ncols = gfiles[i].into_ncols;
-    sum_kmers += gfiles[i].num_kmers < 0 ? 0 : (size_t)gfiles[i].num_kmers;
-    for (size_t j = 0; j < gfiles[i].nfilter; j++) gfiles[i].filter[j].into = 0;
-    gfiles[i].into_ncols = 1;
-  }
-  const size_t kmer_size = gfiles[0].kmer_size, W = gfiles[0].num_words;
+  graph_files in;
+  graph_files_open(argv + optind, (size_t)(argc - optind), reads_usage, &in);
+  graph_files_flatten(&in);
+  const size_t kmer_size = in.files[0].kmer_size, W = in.files[0].num_words;
 
   /* inputs_attempt_open: every output before anything is loaded; on a failure nothing of this run stays behind */
   for (size_t i = 0; i < ntasks; i++) {
@@ -363,27 +330,21 @@ int ctx_reads(int argc, char **argv)
   }
 
   const size_t bits_per_kmer = W * 64; /* sizeof(BinaryKmer) * 8 */
+  /* a table that cannot be sized or a machine without a device: the outputs created above go away again */
   table_plan plan;
-  char ebuf[256], s1[64], s2[64];
-  const char *err = table_plan_for_build(mem_to_use, mem_set, num_kmers_arg, nkmers_set, bits_per_kmer, (int64_t)sum_kmers, &plan,
-                                         ebuf, sizeof(ebuf));
+  mcx_graph *g = NULL;
+  const char *err = table_plan_for_args(&mem, bits_per_kmer, (int64_t)in.sum_kmers, &plan);
+  if (!err) {
+    table_plan_status(&plan);
+    err = graph_table_create(&g, &plan, kmer_size, 1, device);
+  }
   if (err) {
     for (size_t j = 0; j < ntasks; j++) seq_out_close(tasks[j].out, true);
     die("%s", err);
   }
-  status("[memory] graph: %s", bytes_to_str(plan.bytes, 1, s1));
-
-  if (mcx_device_count() < 1) {
-    for (size_t j = 0; j < ntasks; j++) seq_out_close(tasks[j].out, true);
-    die("No MI355X / HIP device found: %s has no CPU build path", CMD_NAME);
-  }
-  mcx_graph *g = NULL;
-  check(mcx_graph_create(&g, (int)kmer_size, 1, plan.capacity, (int)device), "Cannot allocate graph");
-  for (size_t i = 0; i < nfiles; i++) { ctx_load_graph_file(g, &gfiles[i]); ctx_reader_close(&gfiles[i]); }
-  free(gfiles);
-  uint64_t slots = 0, tbytes = 0;
-  mcx_graph_capacity(g, &slots, &tbytes);
-  status("[hasht] Allocated table in HBM with %s entries, using %s", ulong_to_str(slots, s1), bytes_to_str(tbytes, 1, s2));
+  for (size_t i = 0; i < in.n; i++) { ctx_load_graph_file(g, &in.files[i]); ctx_reader_close(&in.files[i]); }
+  free(in.files);
+  hasht_status(g);
 
   status("Printing reads that do %stouch the graph\n", invert ? "not " : "");
 

@@ -13,8 +13,6 @@
 
 #include "../../include/mcx_gpu.h"
 
-#define DEFAULT_MEM (1UL << 29) /* cmd.h:13 */
-
 static const char sort_usage[] =
 "usage: " CMD_NAME " sort [options] <in.ctx>\n"
 "\n"
@@ -34,13 +32,6 @@ static struct option sort_opts[] = {
   {"out", required_argument, NULL, 'o'},     {"device", required_argument, NULL, 'D'},
   {NULL, 0, NULL, 0}};
 
-static void optname(const struct option *opts, char c, char *out)
-{
-  sprintf(out, "-%c, --Unknown", c);
-  for (int i = 0; opts[i].name; i++)
-    if (opts[i].val == c) sprintf(out, "-%c, --%s", c, opts[i].name);
-}
-
 /* futil_create_output (file_util.c:139-174) */
 static void create_output(const char *path, bool force)
 {
@@ -56,25 +47,19 @@ static void create_output(const char *path, bool force)
 int ctx_sort(int argc, char **argv)
 {
   const char *out_path = NULL;
-  size_t mem_to_use = DEFAULT_MEM, num_kmers_arg = 0;
-  bool mem_set = false, nkmers_set = false, force = false;
+  cmd_mem_args margs = CMD_MEM_ARGS_INIT;
+  bool force = false;
   unsigned device = 0;
   char cmd[100];
   int c;
   optind = 1;
   while ((c = getopt_long_only(argc, argv, "hfm:n:o:D:", sort_opts, NULL)) != -1) {
-    optname(sort_opts, (char)c, cmd);
+    cmd_optname(sort_opts, c, cmd);
     switch (c) {
       case 'h': print_usage(sort_usage, NULL);
       case 'f': if (force) print_usage(sort_usage, "%s given twice", cmd); force = true; break;
-      case 'm':
-        if (mem_set) print_usage(sort_usage, "-m, --memory <M> specifed more than once");
-        if (!mem_to_integer(optarg, &mem_to_use) || !mem_to_use) print_usage(sort_usage, "Invalid memory argument: %s", optarg);
-        mem_set = true; break;
-      case 'n':
-        if (nkmers_set) print_usage(sort_usage, "-n, --nkmers <N> specifed more than once");
-        if (!mem_to_integer(optarg, &num_kmers_arg) || !num_kmers_arg) print_usage(sort_usage, "Invalid hash size: %s", optarg);
-        nkmers_set = true; break;
+      case 'm': cmd_mem_set_memory(&margs, sort_usage, optarg); break;
+      case 'n': cmd_mem_set_nkmers(&margs, sort_usage, optarg); break;
       case 'o': if (out_path) print_usage(sort_usage, "%s given twice", cmd); out_path = optarg; break;
       case 'D': if (!parse_entire_uint(optarg, &device)) print_usage(sort_usage, "%s requires an int x >= 0: %s", cmd, optarg); break;
       case ':': case '?': die("`" CMD_NAME " sort -h` for help. Bad option: %s", argv[optind - 1]);
@@ -90,8 +75,8 @@ int ctx_sort(int argc, char **argv)
 
   size_t num_kmers;
   if (r.num_kmers < 0) {
-    if (!nkmers_set) die("If reading from a stream, must give -n <num_kmers>");
-    num_kmers = num_kmers_arg;
+    if (!margs.nkmers_set) die("If reading from a stream, must give -n <num_kmers>");
+    num_kmers = margs.num_kmers;
   } else num_kmers = (size_t)r.num_kmers;
 
   FILE *fout = NULL;
@@ -106,7 +91,7 @@ int ctx_sort(int argc, char **argv)
   const size_t memory = (sizeof(char *) + kmer_mem) * num_kmers;
   char mem_str[64];
   bytes_to_str(memory, 1, mem_str);
-  if (memory > mem_to_use) die("Require at least %s memory", mem_str);
+  if (memory > margs.mem_to_use) die("Require at least %s memory", mem_str);
   status("[memory] Total: %s", mem_str);
 
   unsigned char *mem = malloc(kmer_mem * num_kmers + 1);
@@ -115,7 +100,7 @@ int ctx_sort(int argc, char **argv)
   if (nkread != num_kmers * kmer_mem) die("Could only read %zu bytes [<%zu]", nkread, num_kmers * kmer_mem);
   char tmpc;
   if (fread(&tmpc, 1, 1, r.fh) != 0) die("More kmers in file than believed (kmers: %zu ncols: %zu).", num_kmers, ncols);
-  status("Read %zu kmers with %zu colour%s", num_kmers, ncols, ncols == 1 ? "" : "s");
+  status("Read %zu kmers with %zu colour%s", num_kmers, ncols, plural(ncols));
 
   if (mcx_device_count() < 1) die("No MI355X / HIP device found: %s has no CPU build path", CMD_NAME);
   int rc = mcx_sort_records(mem, num_kmers, (int)r.kmer_size, (int)ncols, (int)device);
@@ -167,7 +152,7 @@ int ctx_index(int argc, char **argv)
   int c;
   optind = 1;
   while ((c = getopt_long_only(argc, argv, "hfo:s:b:D:", index_opts, NULL)) != -1) {
-    optname(index_opts, (char)c, cmd);
+    cmd_optname(index_opts, c, cmd);
     switch (c) {
       case 'h': print_usage(index_usage, NULL);
       case 'f': force = true; break;
@@ -255,7 +240,7 @@ int ctx_index(int argc, char **argv)
   free(blk);
   char a[64], b[64], c2[64], d[64];
   status("Read %s kmers in %s block%s (block size %s / %s kmers)", ulong_to_str(bl_kmer_offset, a), ulong_to_str(nblocks, b),
-         nblocks == 1 ? "" : "s", bytes_to_str(block_size, 1, c2), ulong_to_str(block_kmers, d));
+         plural(nblocks), bytes_to_str(block_size, 1, c2), ulong_to_str(block_kmers, d));
   if (fout != stdout) status("Saved to %s", out_path);
   ctx_reader_close(&r);
   if (fout != stdout) fclose(fout); else fflush(fout);

@@ -11,7 +11,6 @@
 #define _GNU_SOURCE
 #include "host.h"
 
-#include <errno.h>
 #include <getopt.h>
 #include <stdlib.h>
 #include <string.h>
@@ -19,7 +18,6 @@
 
 #include "../../include/mcx_gpu.h"
 
-#define DEFAULT_MEM (1UL << 29) /* cmd.h:13 */
 #define SEED_BATCH_BASES (32UL << 20)
 
 static const char subgraph_usage[] =
@@ -58,29 +56,8 @@ static struct option longopts[] = {
   {"sort", no_argument, NULL, OPT_SORT},      {"device", required_argument, NULL, OPT_DEVICE},
   {NULL, 0, NULL, 0}};
 
-static void optname(int c, char *out)
-{
-  sprintf(out, "-%c, --Unknown", (char)c);
-  for (int i = 0; longopts[i].name; i++)
-    if (longopts[i].val == c) {
-      if (c < 256) sprintf(out, "-%c, --%s", (char)c, longopts[i].name);
-      else sprintf(out, "--%s", longopts[i].name);
-    }
-}
-
-static void check(int rc, const char *what)
-{
-  if (rc == MCX_ERR_FULL) die("Hash table is full");
-  if (rc != MCX_OK) die("%s: %s", what, mcx_last_error());
-}
-
-static const char *plural(uint64_t n) { return n == 1 ? "" : "s"; }
-static const char *outpath(const char *p) { return strcmp(p, "-") ? p : "STDOUT"; }
-
-static int write_sink(void *ctx, const void *recs, size_t nbytes)
-{
-  return fwrite(recs, 1, nbytes, (FILE *)ctx) == nbytes ? 0 : 1;
-}
+/* -x given twice */
+#define ONCE(seen) do { if (seen) print_usage(subgraph_usage, "%s given twice", cmd); } while (0)
 
 static void str_append(char **s, size_t *len, const char *add)
 {
@@ -94,8 +71,8 @@ static void str_append(char **s, size_t *len, const char *add)
 int ctx_subgraph(int argc, char **argv)
 {
   const char *out_path = NULL;
-  size_t mem_to_use = DEFAULT_MEM, num_kmers_arg = 0;
-  bool mem_set = false, nkmers_set = false, force = false, sort_kmers = false, invert = false, grab_unitigs = false;
+  cmd_mem_args mem = CMD_MEM_ARGS_INIT;
+  bool force = false, sort_kmers = false, invert = false, grab_unitigs = false;
   bool dist_set = false;
   unsigned nthreads = 0, device = 0, use_ncols = 0, dist = 0;
   seq_in **seeds = NULL;
@@ -104,25 +81,16 @@ int ctx_subgraph(int argc, char **argv)
   int c;
   optind = 1;
   while ((c = getopt_long_only(argc, argv, "hfo:m:n:t:N:s:1:d:vU", longopts, NULL)) != -1) {
-    optname(c, cmd);
+    cmd_optname(longopts, c, cmd);
     switch (c) {
       case 'h': print_usage(subgraph_usage, NULL);
-      case 'f': if (force) print_usage(subgraph_usage, "%s given twice", cmd); force = true; break;
-      case 'o': if (out_path) print_usage(subgraph_usage, "%s given twice", cmd); out_path = optarg; break;
-      case 't':
-        if (nthreads) print_usage(subgraph_usage, "%s given twice", cmd);
-        if (!parse_entire_uint(optarg, &nthreads) || !nthreads) print_usage(subgraph_usage, "%s requires an int x > 0", cmd);
-        break;
-      case 'm':
-        if (mem_set) print_usage(subgraph_usage, "-m, --memory <M> specifed more than once");
-        if (!mem_to_integer(optarg, &mem_to_use) || !mem_to_use) print_usage(subgraph_usage, "Invalid memory argument: %s", optarg);
-        mem_set = true; break;
-      case 'n':
-        if (nkmers_set) print_usage(subgraph_usage, "-n, --nkmers <N> specifed more than once");
-        if (!mem_to_integer(optarg, &num_kmers_arg) || !num_kmers_arg) print_usage(subgraph_usage, "Invalid hash size: %s", optarg);
-        nkmers_set = true; break;
+      case 'f': ONCE(force); force = true; break;
+      case 'o': ONCE(out_path); out_path = optarg; break;
+      case 't': cmd_threads_arg(&nthreads, subgraph_usage, cmd, optarg); break;
+      case 'm': cmd_mem_set_memory(&mem, subgraph_usage, optarg); break;
+      case 'n': cmd_mem_set_nkmers(&mem, subgraph_usage, optarg); break;
       case 'N':
-        if (use_ncols) print_usage(subgraph_usage, "%s given twice", cmd);
+        ONCE(use_ncols);
         if (!parse_entire_uint(optarg, &use_ncols) || !use_ncols) print_usage(subgraph_usage, "%s requires an int x > 0", cmd);
         break;
       case '1':
@@ -135,12 +103,12 @@ int ctx_subgraph(int argc, char **argv)
         break;
       }
       case 'd':
-        if (dist_set && dist) print_usage(subgraph_usage, "%s given twice", cmd); /* cmd_check(!dist, cmd) */
+        ONCE(dist_set && dist); /* cmd_check(!dist, cmd) */
         if (!parse_entire_uint(optarg, &dist)) print_usage(subgraph_usage, "%s requires an int x >= 0: %s", cmd, optarg);
         dist_set = true; break;
-      case 'v': if (invert) print_usage(subgraph_usage, "%s given twice", cmd); invert = true; break;
-      case 'U': if (grab_unitigs) print_usage(subgraph_usage, "%s given twice", cmd); grab_unitigs = true; break;
-      case OPT_SORT: if (sort_kmers) print_usage(subgraph_usage, "%s given twice", cmd); sort_kmers = true; break;
+      case 'v': ONCE(invert); invert = true; break;
+      case 'U': ONCE(grab_unitigs); grab_unitigs = true; break;
+      case OPT_SORT: ONCE(sort_kmers); sort_kmers = true; break;
       case OPT_DEVICE: if (!parse_entire_uint(optarg, &device)) print_usage(subgraph_usage, "%s requires an int x >= 0: %s", cmd, optarg); break;
       case ':': case '?': die("`" CMD_NAME " subgraph -h` for help. Bad option: %s", argv[optind - 1]);
       default: abort();
@@ -151,21 +119,9 @@ int ctx_subgraph(int argc, char **argv)
   if (optind >= argc) print_usage(subgraph_usage, "Require input graph files (.ctx)");
   if (out_path == NULL) out_path = "-";
 
-  /* graph_files_open: each file's colours go after those of the files before it unless its filter says otherwise */
-  const size_t nfiles = (size_t)(argc - optind);
-  ctx_reader *gfiles = calloc(nfiles, sizeof(ctx_reader));
-  if (!gfiles) die("Out of memory");
-  size_t ncols = 0, max_kmers = 0, sum_kmers = 0;
-  for (size_t i = 0; i < nfiles; i++) {
-    ctx_reader_open(&gfiles[i], argv[optind + (int)i], ncols, MIN_KMER_SIZE, MAX_KMER_SIZE);
-    if (gfiles[i].kmer_size != gfiles[0].kmer_size)
-      print_usage(subgraph_usage, "Kmer sizes don't match [%u vs %u]", gfiles[0].kmer_size, gfiles[i].kmer_size);
-    if (gfiles[i].into_ncols > ncols) ncols = gfiles[i].into_ncols;
-    const size_t nk = gfiles[i].num_kmers < 0 ? 0 : (size_t)gfiles[i].num_kmers;
-    if (nk > max_kmers) max_kmers = nk;
-    sum_kmers += nk;
-  }
-  const size_t kmer_size = gfiles[0].kmer_size, W = gfiles[0].num_words;
+  graph_files in;
+  graph_files_open(argv + optind, (size_t)(argc - optind), subgraph_usage, &in);
+  const size_t ncols = in.ncols, kmer_size = in.files[0].kmer_size, W = in.files[0].num_words;
 
   /* futil_create_output */
   if (strcmp(out_path, "-") != 0 && !force && access(out_path, F_OK) == 0) die("File already exists: %s", out_path);
@@ -173,29 +129,22 @@ int ctx_subgraph(int argc, char **argv)
   /* ---- memory: as `popbubbles` sizes the table for the same inputs ---- */
   const size_t bits_per_kmer = W * 64 + (4 + 1) * 8 * ncols + 2 + (sort_kmers ? 64 : 0);
   table_plan plan;
-  char ebuf[256], s1[64], s2[64];
-  const char *err = table_plan_for_build(mem_to_use, mem_set, num_kmers_arg, nkmers_set, bits_per_kmer, (int64_t)sum_kmers, &plan,
-                                         ebuf, sizeof(ebuf));
+  char s1[64], s2[64];
+  const char *err = table_plan_for_args(&mem, bits_per_kmer, (int64_t)in.sum_kmers, &plan);
   if (err) die("%s", err);
-  status("[memory] graph: %s", bytes_to_str(plan.bytes, 1, s1));
-
-  if (mcx_device_count() < 1) die("No MI355X / HIP device found: %s has no CPU build path", CMD_NAME);
+  table_plan_status(&plan);
   mcx_graph *g = NULL;
-  check(mcx_graph_create(&g, (int)kmer_size, (int)ncols, plan.capacity, (int)device), "Cannot allocate graph");
+  if ((err = graph_table_create(&g, &plan, kmer_size, ncols, device))) die("%s", err);
 
   /* the output header: graph_file_merge_header of every input, then the intersection name on every colour */
-  col_info *cols = malloc(ncols * sizeof(col_info));
-  if (!cols) die("Out of memory");
-  for (size_t i = 0; i < ncols; i++) col_info_init(&cols[i]);
+  col_info *cols = graph_files_merge_headers(&in, ncols);
   char *gname = NULL;
   size_t gname_len = 0;
   str_append(&gname, &gname_len, "subgraph:{");
   bool first = true;
-  for (size_t i = 0; i < nfiles; i++)
-    for (size_t j = 0; j < gfiles[i].nfilter; j++) {
-      const col_info *src = &gfiles[i].ginfo[gfiles[i].filter[j].from];
-      col_info_merge(&cols[gfiles[i].filter[j].into], src);
-      /* graph_info_make_intersect */
+  for (size_t i = 0; i < in.n; i++)
+    for (size_t j = 0; j < in.files[i].nfilter; j++) { /* graph_info_make_intersect */
+      const col_info *src = &in.files[i].ginfo[in.files[i].filter[j].from];
       if (!first) str_append(&gname, &gname_len, ",");
       first = false;
       str_append(&gname, &gname_len, src->name);
@@ -218,20 +167,17 @@ int ctx_subgraph(int argc, char **argv)
     }
     ec->is_graph_intersection = 1;
   }
-  for (size_t i = 0; i < nfiles; i++) ctx_load_graph_file(g, &gfiles[i]);
-
-  uint64_t slots = 0, tbytes = 0;
-  mcx_graph_capacity(g, &slots, &tbytes);
-  status("[hasht] Allocated table in HBM with %s entries, using %s", ulong_to_str(slots, s1), bytes_to_str(tbytes, 1, s2));
+  for (size_t i = 0; i < in.n; i++) ctx_load_graph_file(g, &in.files[i]);
+  hasht_status(g);
 
   /* subgraph_from_reads */
   const uint32_t flags = (grab_unitigs ? MCX_SUBGRAPH_UNITIGS : 0) | (invert ? MCX_SUBGRAPH_INVERT : 0);
-  check(mcx_graph_subgraph_begin(g, flags), "subgraph");
+  mcx_check(mcx_graph_subgraph_begin(g, flags), "subgraph");
   read_batch batch;
   read_batch_init(&batch, false);
   for (size_t i = 0; i < nseeds; i++) {
     while (seq_in_fill(seeds[i], &batch, SEED_BATCH_BASES) > 0 || batch.nreads) {
-      check(mcx_graph_subgraph_seed_reads(g, batch.bases, batch.offsets, batch.nreads), "subgraph seeds");
+      mcx_check(mcx_graph_subgraph_seed_reads(g, batch.bases, batch.offsets, batch.nreads), "subgraph seeds");
       read_batch_clear(&batch);
     }
     seq_in_close(seeds[i]);
@@ -244,27 +190,15 @@ int ctx_subgraph(int argc, char **argv)
   if (invert) status("Inverting selection...");
   status("Pruning untouched nodes...");
   mcx_subgraph_stats st;
-  check(mcx_graph_subgraph_finish(g, dist, flags, &st), "subgraph");
+  mcx_check(mcx_graph_subgraph_finish(g, dist, flags, &st), "subgraph");
   status("Found %s / %s (%.2f%%) seed kmers", ulong_to_str(st.num_seed_found, s1), ulong_to_str(st.num_seed_kmers, s2),
          (100.0 * (double)st.num_seed_found) / (double)st.num_seed_kmers);
 
-  uint64_t nk = 0;
-  check(mcx_graph_nkmers(g, &nk), "nkmers");
-  FILE *fout = stdout;
-  if (strcmp(out_path, "-") != 0) {
-    fout = fopen(out_path, "wb");
-    if (!fout) die("Cannot open output file: %s [%s]", out_path, strerror(errno));
-  }
-  const size_t hdr = ctx_write_header(fout, (uint32_t)kmer_size, (uint32_t)ncols, cols);
-  check(mcx_graph_export(g, sort_kmers ? 1 : 0, write_sink, fout), "export");
-  if (fflush(fout) != 0) die("Cannot write to file: %s", out_path);
-  status("Dumped %s kmers in %zu colour%s into: %s (format version: 6; %s)", ulong_to_str(nk, s1), ncols, plural(ncols),
-         outpath(out_path), bytes_to_str(hdr + nk * (8 * W + 5 * ncols), 1, s2));
-  if (fout != stdout && fclose(fout) != 0) die("Cannot write to file: %s", out_path);
+  ctx_write_graph(g, out_path, kmer_size, ncols, cols, sort_kmers);
 
-  for (size_t i = 0; i < ncols; i++) col_info_free(&cols[i]);
-  for (size_t i = 0; i < nfiles; i++) ctx_reader_close(&gfiles[i]);
-  free(cols); free(gfiles); free(gname);
+  col_infos_free(cols, ncols);
+  graph_files_close(&in);
+  free(gname);
   mcx_graph_destroy(g);
   return EXIT_SUCCESS;
 }

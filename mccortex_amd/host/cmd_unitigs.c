@@ -13,8 +13,6 @@
 
 #include "../../include/mcx_gpu.h"
 
-#define DEFAULT_MEM (1UL << 29) /* cmd.h:13 */
-
 static const char unitigs_usage[] =
 "usage: " CMD_NAME " unitigs [options] <in.ctx> [<in2.ctx> ...]\n"
 "\n"
@@ -46,58 +44,34 @@ static struct option longopts[] = {
 
 static const char *syntax_strs[3] = {"FASTA", "GFA", "DOT (Graphviz)"};
 
-static void optname(char c, char *out)
-{
-  sprintf(out, "-%c, --Unknown", c);
-  for (int i = 0; longopts[i].name; i++)
-    if (longopts[i].val == c) sprintf(out, "-%c, --%s", c, longopts[i].name);
-}
-
-static void check(int rc, const char *what)
-{
-  if (rc == MCX_ERR_FULL) die("Hash table is full");
-  if (rc != MCX_OK) die("%s: %s", what, mcx_last_error());
-}
-
-static int write_sink(void *ctx, const void *text, size_t nbytes)
-{
-  return fwrite(text, 1, nbytes, (FILE *)ctx) == nbytes ? 0 : 1;
-}
+/* -x given twice */
+#define ONCE(seen) do { if (seen) print_usage(unitigs_usage, "%s given twice", cmd); } while (0)
 
 int ctx_unitigs(int argc, char **argv)
 {
   const char *out_path = NULL;
-  size_t mem_to_use = DEFAULT_MEM, num_kmers_arg = 0;
-  bool mem_set = false, nkmers_set = false, force = false, points = false;
+  cmd_mem_args mem = CMD_MEM_ARGS_INIT;
+  bool force = false, points = false;
   unsigned nthreads = 0, device = 0;
   int syntax = MCX_UNITIGS_FASTA;
   char cmd[100];
   int c;
   optind = 1;
   while ((c = getopt_long_only(argc, argv, "ho:fm:n:t:D:FgdP", longopts, NULL)) != -1) {
-    optname((char)c, cmd);
+    cmd_optname(longopts, c, cmd);
     switch (c) {
       case 'h': print_usage(unitigs_usage, NULL);
-      case 'f': if (force) print_usage(unitigs_usage, "%s given twice", cmd); force = true; break;
-      case 'o': if (out_path) print_usage(unitigs_usage, "%s given twice", cmd); out_path = optarg; break;
-      case 't':
-        if (nthreads) print_usage(unitigs_usage, "%s given twice", cmd);
-        if (!parse_entire_uint(optarg, &nthreads) || !nthreads) print_usage(unitigs_usage, "%s requires an int x > 0", cmd);
-        break;
-      case 'm':
-        if (mem_set) print_usage(unitigs_usage, "-m, --memory <M> specifed more than once");
-        if (!mem_to_integer(optarg, &mem_to_use) || !mem_to_use) print_usage(unitigs_usage, "Invalid memory argument: %s", optarg);
-        mem_set = true; break;
-      case 'n':
-        if (nkmers_set) print_usage(unitigs_usage, "-n, --nkmers <N> specifed more than once");
-        if (!mem_to_integer(optarg, &num_kmers_arg) || !num_kmers_arg) print_usage(unitigs_usage, "Invalid hash size: %s", optarg);
-        nkmers_set = true; break;
+      case 'f': ONCE(force); force = true; break;
+      case 'o': ONCE(out_path); out_path = optarg; break;
+      case 't': cmd_threads_arg(&nthreads, unitigs_usage, cmd, optarg); break;
+      case 'm': cmd_mem_set_memory(&mem, unitigs_usage, optarg); break;
+      case 'n': cmd_mem_set_nkmers(&mem, unitigs_usage, optarg); break;
       case 'D': if (!parse_entire_uint(optarg, &device)) print_usage(unitigs_usage, "%s requires an int x >= 0: %s", cmd, optarg); break;
       /* cmd_check(!syntax, cmd): a format option after a non-FASTA one is refused, whichever it is */
-      case 'F': if (syntax) print_usage(unitigs_usage, "%s given twice", cmd); syntax = MCX_UNITIGS_FASTA; break;
-      case 'g': if (syntax) print_usage(unitigs_usage, "%s given twice", cmd); syntax = MCX_UNITIGS_GFA; break;
-      case 'd': if (syntax) print_usage(unitigs_usage, "%s given twice", cmd); syntax = MCX_UNITIGS_DOT; break;
-      case 'P': if (points) print_usage(unitigs_usage, "%s given twice", cmd); points = true; break;
+      case 'F': ONCE(syntax); syntax = MCX_UNITIGS_FASTA; break;
+      case 'g': ONCE(syntax); syntax = MCX_UNITIGS_GFA; break;
+      case 'd': ONCE(syntax); syntax = MCX_UNITIGS_DOT; break;
+      case 'P': ONCE(points); points = true; break;
       case ':': case '?': die("`" CMD_NAME " unitigs -h` for help. Bad option: %s", argv[optind - 1]);
       default: abort();
     }
@@ -109,29 +83,18 @@ int ctx_unitigs(int argc, char **argv)
   if (points && syntax != MCX_UNITIGS_DOT) print_usage(unitigs_usage, "--points only valid with --graphviz / --dot");
 
   /* graph_files_open, then file_filter_flatten(.., 0): every colour of every file goes into colour 0 */
-  const size_t nfiles = (size_t)(argc - optind);
-  ctx_reader *gfiles = calloc(nfiles, sizeof(ctx_reader));
-  if (!gfiles) die("Out of memory");
-  size_t file_ncols = 0, sum_kmers = 0;
-  for (size_t i = 0; i < nfiles; i++) {
-    ctx_reader_open(&gfiles[i], argv[optind + (int)i], file_ncols, MIN_KMER_SIZE, MAX_KMER_SIZE);
-    if (gfiles[i].kmer_size != gfiles[0].kmer_size)
-      print_usage(unitigs_usage, "Kmer sizes don't match [%u vs %u]", gfiles[0].kmer_size, gfiles[i].kmer_size);
-    if (gfiles[i].into_ncols > file_ncols) file_ncols = gfiles[i].into_ncols;
-    sum_kmers += gfiles[i].num_kmers < 0 ? 0 : (size_t)gfiles[i].num_kmers;
-    for (size_t j = 0; j < gfiles[i].nfilter; j++) gfiles[i].filter[j].into = 0;
-    gfiles[i].into_ncols = 1;
-  }
-  const size_t kmer_size = gfiles[0].kmer_size, W = gfiles[0].num_words;
+  graph_files in;
+  graph_files_open(argv + optind, (size_t)(argc - optind), unitigs_usage, &in);
+  graph_files_flatten(&in);
+  const size_t kmer_size = in.files[0].kmer_size, W = in.files[0].num_words;
 
   const size_t bits_per_kmer = W * 64 + (4 + 1) * 8 + 1;
   table_plan plan;
-  char ebuf[256], s1[64], s2[64];
-  const char *err = table_plan_for_build(mem_to_use, mem_set, num_kmers_arg, nkmers_set, bits_per_kmer, (int64_t)sum_kmers, &plan,
-                                         ebuf, sizeof(ebuf));
+  char s1[64];
+  const char *err = table_plan_for_args(&mem, bits_per_kmer, (int64_t)in.sum_kmers, &plan);
   if (err) die("%s", err);
-  status("[memory] graph: %s", bytes_to_str(plan.bytes, 1, s1));
-  status("Output in %s format to %s\n", syntax_strs[syntax], strcmp(out_path, "-") ? out_path : "STDOUT");
+  table_plan_status(&plan);
+  status("Output in %s format to %s\n", syntax_strs[syntax], outpath(out_path));
 
   /* futil_fopen_create: an existing file is kept unless --force */
   FILE *fout = stdout;
@@ -141,23 +104,19 @@ int ctx_unitigs(int argc, char **argv)
     if (!fout) die("Cannot open output file: %s [%s]", out_path, strerror(errno));
   }
 
-  if (mcx_device_count() < 1) die("No MI355X / HIP device found: %s has no CPU build path", CMD_NAME);
   mcx_graph *g = NULL;
-  check(mcx_graph_create(&g, (int)kmer_size, 1, plan.capacity, (int)device), "Cannot allocate graph");
-  for (size_t i = 0; i < nfiles; i++) ctx_load_graph_file(g, &gfiles[i]);
-  uint64_t slots = 0, tbytes = 0;
-  mcx_graph_capacity(g, &slots, &tbytes);
-  status("[hasht] Allocated table in HBM with %s entries, using %s", ulong_to_str(slots, s1), bytes_to_str(tbytes, 1, s2));
+  if ((err = graph_table_create(&g, &plan, kmer_size, 1, device))) die("%s", err);
+  for (size_t i = 0; i < in.n; i++) ctx_load_graph_file(g, &in.files[i]);
+  hasht_status(g);
 
   if (syntax == MCX_UNITIGS_FASTA) status("Printing unitgs in FASTA using %u threads", nthreads);
   mcx_unitigs_stats st = {0, 0, 0, 0};
-  check(mcx_graph_unitigs(g, syntax, points ? MCX_UNITIGS_POINTS : 0, write_sink, fout, &st), "unitigs");
+  mcx_check(mcx_graph_unitigs(g, syntax, points ? MCX_UNITIGS_POINTS : 0, write_sink, fout, &st), "unitigs");
   if (fflush(fout) != 0) die("Cannot write to file: %s", out_path);
   status("Dumped %s unitigs\n", ulong_to_str(st.num_unitigs, s1));
   if (fout != stdout && fclose(fout) != 0) die("Cannot write to file: %s", out_path);
 
-  for (size_t i = 0; i < nfiles; i++) ctx_reader_close(&gfiles[i]);
-  free(gfiles);
+  graph_files_close(&in);
   mcx_graph_destroy(g);
   return EXIT_SUCCESS;
 }

@@ -1,6 +1,6 @@
-/* host.h -- C host side of `mccortex<K> build` over the MI355X backend (include/mcx_gpu.h).
- * Mirrors the reference's command surface: src/main/mccortex.c (dispatcher),
- * src/commands/ctx_build.c (options, batching, sizing), src/graph/graph_writer.c (.ctx v6). */
+/* host.h -- C host side of the `mccortex<K>` commands over the MI355X backend (include/mcx_gpu.h).
+ * Mirrors the reference's command surface: src/main/mccortex.c (dispatcher), src/commands/ctx_*.c (options, messages,
+ * flow), src/basic/cmd.c and src/graph/cmd_mem.c (shared option handling), src/graph/graph_writer.c (.ctx v6). */
 #ifndef MCX_HOST_H_
 #define MCX_HOST_H_
 
@@ -143,6 +143,50 @@ void ctx_reader_close(ctx_reader *r);
 int cleaning_pick_kmer_threshold(const uint64_t *kmer_covg, size_t arrlen, double *alpha_est, double *beta_est,
                                  double *false_pos, double *false_neg);
 
+/* ---- shared by the commands (cmd_common.c; calls into libmcxgpu, so not part of libmcxhost.so) ---- */
+struct option;
+struct mcx_graph;
+#define DEFAULT_MEM (1UL << 29) /* cmd.h:13 */
+/* cmd_get_longopt_str: "-x, --name" for c < 256, "--name" for a long-only option, "-x, --Unknown" without a match */
+void cmd_optname(const struct option *opts, int c, char *out);
+void mcx_check(int rc, const char *what); /* dies with "Hash table is full" or "<what>: <mcx_last_error()>" */
+int write_sink(void *ctx, const void *data, size_t nbytes); /* export sink: fwrite to the FILE * in ctx */
+const char *plural(uint64_t n);
+const char *outpath(const char *p); /* "-" reads STDOUT */
+/* -m / -n / -t (cmd_mem_args_set_memory, cmd_mem_args_set_nkmers; cmd_uint32_nonzero after cmd_check(!nthreads)) */
+typedef struct { size_t mem_to_use, num_kmers; bool mem_set, nkmers_set; } cmd_mem_args;
+#define CMD_MEM_ARGS_INIT {DEFAULT_MEM, 0, false, false}
+void cmd_mem_set_memory(cmd_mem_args *m, const char *usage, const char *arg);
+void cmd_mem_set_nkmers(cmd_mem_args *m, const char *usage, const char *arg);
+void cmd_threads_arg(unsigned *nthreads, const char *usage, const char *cmd, const char *arg);
+/* graph_files_open: the input graphs, each at the running colour offset; ncols = colours they load into */
+typedef struct { ctx_reader *files; size_t n, ncols, max_kmers, sum_kmers; } graph_files;
+void graph_files_open(char **paths, size_t n, const char *usage, graph_files *set);
+void graph_files_flatten(graph_files *set); /* every colour of every file into colour 0 */
+void graph_files_close(graph_files *set);
+col_info *graph_files_merge_headers(const graph_files *set, size_t ncols); /* col_info[ncols]: the output header */
+void col_infos_free(col_info *cols, size_t ncols);
+/* the table in HBM: size it from -m / -n (NULL, or why it cannot be: the caller dies, after any cleaning up of its
+ * own), report it, create it (NULL, or the refusal of a machine without a device), report what was allocated */
+const char *table_plan_for_args(const cmd_mem_args *m, size_t bits_per_kmer, int64_t nkmers, table_plan *plan);
+void table_plan_status(const table_plan *plan); /* "[memory] graph: ..." */
+const char *graph_table_create(struct mcx_graph **g, const table_plan *plan, size_t kmer_size, size_t ncols, unsigned device);
+void hasht_status(struct mcx_graph *g); /* "[hasht] Allocated table in HBM ..." */
+/* graph_load: the records of an opened file into the table, colour filter[i].from into filter[i].into; dies on a short
+ * tail or an oversized k-mer, warns when the header's k-mer count is off, ends with "[GReader] Loaded ..." */
+typedef struct {
+  int into_all;       /* >= 0: every colour goes into this one, whatever the filter says */
+  uint32_t rec_flags; /* MCX_RECORDS_* */
+  bool warn_covg;     /* warn once each about a k-mer without coverage and one with edges but no coverage */
+  unsigned char *buf; /* the caller's chunk buffer of buf_bytes; NULL: 64 MiB of the loader's own */
+  size_t buf_bytes;
+} graph_load_opts;
+void graph_load(struct mcx_graph *g, ctx_reader *r, const graph_load_opts *opts); /* opts NULL: {-1, 0, false, NULL, 0} */
+void ctx_load_graph_file(struct mcx_graph *g, ctx_reader *r); /* "[GReader] N kmers, S filesize", then graph_load */
+/* header, every record of the table, the "Dumped ..." line; "-" is stdout */
+void ctx_write_graph(struct mcx_graph *g, const char *out_path, size_t kmer_size, size_t ncols, const col_info *cols, bool sort_kmers);
+void ctx_dumped_status(uint64_t nkmers, size_t kmer_size, size_t ncols, size_t hdr_bytes, const char *out_path);
+
 /* ---- commands ---- */
 int ctx_build(int argc, char **argv);
 int ctx_sort(int argc, char **argv);
@@ -153,6 +197,7 @@ int ctx_pop_bubbles(int argc, char **argv); /* src/commands/ctx_pop_bubbles.c */
 int ctx_subgraph(int argc, char **argv);    /* src/commands/ctx_subgraph.c */
 int ctx_unitigs(int argc, char **argv);     /* src/commands/ctx_unitigs.c */
 int ctx_reads(int argc, char **argv);       /* src/commands/ctx_reads.c */
+int ctx_hashtest(int argc, char **argv);    /* src/commands/ctx_exp_hashtest.c */
 
 /* ---- sequence output of `reads` (src/basic/seqout.{h,c}): <O>.fq.gz / .fa.gz / .txt.gz, for a paired task also
  * <O>.1.* and <O>.2.*; files are created with O_EXCL unless `force`, directories as needed (seq_out.c) ---- */
@@ -162,9 +207,5 @@ seq_out *seq_out_open(const char *out_base, seq_fmt fmt, bool is_pe, bool force)
 /* read i of the batch into the unpaired file (which = 0) or into <O>.1 / <O>.2 (which = 1 / 2) */
 void seq_out_print(seq_out *o, int which, const read_batch *b, size_t i);
 void seq_out_close(seq_out *o, bool rm); /* rm: delete the files as well */
-/* graph_load: one opened file's colours through its filter into the device table (cmd_clean.c) */
-struct mcx_graph;
-void ctx_load_graph_file(struct mcx_graph *g, ctx_reader *r);
-int ctx_hashtest(int argc, char **argv); /* src/commands/ctx_exp_hashtest.c */
 
 #endif

@@ -1,4 +1,4 @@
-/* host_util.c -- logging, number parsing, table sizing for the `build` host program. */
+/* host_util.c -- logging, number parsing, table sizing for the `mccortex<K>` host programs. */
 #define _GNU_SOURCE
 #include "host.h"
 
