@@ -57,15 +57,42 @@ static int fail(int code, const char *fmt, ...)
                   #expr, hipGetErrorString(_e), __FILE__, __LINE__);                           \
   } while (0)
 
-// device scratch that is released on every way out of a function (HIP_TRY returns early)
+// device scratch that is released on every way out of a function (HIP_TRY returns early); borrow() points it at
+// memory somebody else owns, which it then leaves alone
 template <class T> struct DevBuf {
   T *p = nullptr;
+  bool owned = true;
   DevBuf() = default;
   DevBuf(const DevBuf &) = delete;
   DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
+  ~DevBuf() { release(); }
   hipError_t alloc(size_t n) { return hipMalloc((void **)&p, n * sizeof(T)); }
+  void borrow(T *q) { release(); p = q; owned = false; }
+  void release() { if (p && owned) (void)hipFree(p); p = nullptr; owned = true; }
   operator T *() const { return p; }
+};
+// the same for pinned host memory
+template <class T> struct HostBuf {
+  T *p = nullptr;
+  bool owned = true;
+  HostBuf() = default;
+  HostBuf(const HostBuf &) = delete;
+  HostBuf &operator=(const HostBuf &) = delete;
+  ~HostBuf() { release(); }
+  hipError_t alloc(size_t n) { return hipHostMalloc((void **)&p, n * sizeof(T), hipHostMallocDefault); }
+  void borrow(T *q) { release(); p = q; owned = false; }
+  void release() { if (p && owned) (void)hipHostFree(p); p = nullptr; owned = true; }
+  operator T *() const { return p; }
+};
+// runs `fn` on every way out of a scope, unless dismiss() was called: streams, events, a half-built handle
+template <class F> struct ScopeExit {
+  F fn;
+  bool armed = true;
+  explicit ScopeExit(F f) : fn(std::move(f)) {}
+  ScopeExit(const ScopeExit &) = delete;
+  ScopeExit &operator=(const ScopeExit &) = delete;
+  ~ScopeExit() { if (armed) fn(); }
+  void dismiss() { armed = false; }
 };
 
 // Persistent staging threads.  A chunk of 128 Mi positions is packed in ~2 ms: creating and joining
@@ -383,6 +410,7 @@ extern "C" int mcx_graph_create_shard(mcx_graph **out, int kmer_size, int ncols,
   HIP_TRY(hipSetDevice(device));
 
   mcx_graph *g = new mcx_graph();
+  ScopeExit half_built([&] { mcx_graph_destroy(g); });  // dismissed when the handle is handed out
   g->k = kmer_size;
   g->W = words_for_k(kmer_size);
   g->ncols = ncols;
@@ -399,13 +427,12 @@ extern "C" int mcx_graph_create_shard(mcx_graph **out, int kmer_size, int ncols,
     // (owner, region) bins of the sender kernel: at most 2048, and mix_bucket() takes its bits below
     // the lb1 + lbo <= 12 it assumes.  Per shard that is 2048 / shards regions x 2048 sub-tables.
     const uint64_t max_slots = ((uint64_t)kMaxBins << (11 - lbo)) * sub_slots;
-    delete g;
     return fail(MCX_ERR_ARG, "capacity per device too large for a table split over %d devices: %llu slots requested, at most %llu "
                 "(use more devices or a smaller -n / -m)", nparts, (unsigned long long)(nsub * sub_slots), (unsigned long long)max_slots);
   }
   const uint64_t spb = (nsub + (1ull << lb1) - 1) >> lb1;
   nsub = spb << lb1;
-  if (nsub >= (1ull << 31)) { delete g; return fail(MCX_ERR_ARG, "capacity too large"); }
+  if (nsub >= (1ull << 31)) return fail(MCX_ERR_ARG, "capacity too large");
   // overflow area behind the hash-addressed slots (mcx_kernels.h, ovf_start): 1/32 of the table,
   // at least one sub-table's worth
   uint64_t novf = std::max<uint64_t>(sub_slots, (nsub * sub_slots / 32 + sub_slots - 1) / sub_slots * sub_slots);
@@ -435,17 +462,8 @@ extern "C" int mcx_graph_create_shard(mcx_graph **out, int kmer_size, int ncols,
   HIP_TRY(hipGetDeviceProperties(&prop, device));
   g->grid = prop.multiProcessorCount * 8;
 
-#define CREATE_TRY(expr)                                                            \
-  do {                                                                              \
-    hipError_t _e = (expr);                                                         \
-    if (_e != hipSuccess) {                                                         \
-      int rc = fail(_e == hipErrorOutOfMemory ? MCX_ERR_NOMEM : MCX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
-      mcx_graph_destroy(g);                                                         \
-      return rc;                                                                    \
-    }                                                                               \
-  } while (0)
-  CREATE_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-  CREATE_TRY(hipMalloc((void **)&g->t.rec, g->table_bytes));
+  HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+  HIP_TRY(hipMalloc((void **)&g->t.rec, g->table_bytes));
   if (ncols == 1) {
     g->t.KS = g->t.VS = (uint32_t)(g->W + 1);
     g->t.val = g->t.rec + g->W;
@@ -456,21 +474,21 @@ extern "C" int mcx_graph_create_shard(mcx_graph **out, int kmer_size, int ncols,
     g->t.val = g->t.rec + g->t.nslots * (uint64_t)g->W;
     g->t.VC = g->t.nslots;
   }
-  CREATE_TRY(hipMalloc((void **)&g->d_ctr, sizeof(Counters)));
-  CREATE_TRY(hipHostMalloc((void **)&g->h_ctr, sizeof(Counters), hipHostMallocDefault));
-  CREATE_TRY(hipHostMalloc((void **)&g->h_full, sizeof(uint32_t), hipHostMallocDefault));
+  HIP_TRY(hipMalloc((void **)&g->d_ctr, sizeof(Counters)));
+  HIP_TRY(hipHostMalloc((void **)&g->h_ctr, sizeof(Counters), hipHostMallocDefault));
+  HIP_TRY(hipHostMalloc((void **)&g->h_full, sizeof(uint32_t), hipHostMallocDefault));
   *g->h_full = 0;
   g->touch_bytes = (1 + ((g->t.nmain >> sub_shift_for_words(g->W)) + 31) / 32) * 4;
   {  // (kTouchHdr bytes of slow-path counters in front of the flags: TableView::touch)
     uint8_t *tb = nullptr;
-    CREATE_TRY(hipMalloc((void **)&tb, kTouchHdr + g->touch_bytes));
+    HIP_TRY(hipMalloc((void **)&tb, kTouchHdr + g->touch_bytes));
     g->t.touch = reinterpret_cast<uint32_t *>(tb + kTouchHdr);
   }
-  CREATE_TRY(hipMemsetAsync(g->t.rec, 0, g->table_bytes, g->stream));
-  CREATE_TRY(hipMemsetAsync(touch_base(g), 0, kTouchHdr + g->touch_bytes, g->stream));
-  CREATE_TRY(hipMemsetAsync(g->d_ctr, 0, sizeof(Counters), g->stream));
-  CREATE_TRY(hipStreamSynchronize(g->stream));
-#undef CREATE_TRY
+  HIP_TRY(hipMemsetAsync(g->t.rec, 0, g->table_bytes, g->stream));
+  HIP_TRY(hipMemsetAsync(touch_base(g), 0, kTouchHdr + g->touch_bytes, g->stream));
+  HIP_TRY(hipMemsetAsync(g->d_ctr, 0, sizeof(Counters), g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  half_built.dismiss();
   *out = g;
   return MCX_OK;
 }
@@ -603,7 +621,7 @@ struct StreamLaunch {
 // optional per-kernel timing with HIP events on the handle's stream
 struct SpanGuard {
   mcx_graph *g; size_t idx; bool on;
-  SpanGuard(mcx_graph *g_, const char *name) : g(g_), idx(0), on(g_->profile) {
+  SpanGuard(mcx_graph *g_, const char *name) : g(g_), idx(0), on(g_ && g_->profile) {
     if (!on) return;
     mcx_graph::Span sp{name, nullptr, nullptr};
     (void)hipEventCreate(&sp.a); (void)hipEventCreate(&sp.b);
@@ -641,6 +659,52 @@ static void phase_clock(const char *cmd, const char *what, double &t0)
   const double t = now_s();
   fprintf(stderr, "[timing]   %s %8.1f ms  %s\n", cmd, (t - t0) * 1e3, what);
   t0 = t;
+}
+
+// out[i] = in[0] + .. + in[i - 1] in 64 bits (rocprim's size query, its temporary and the scan).  Synchronous.
+template <class In> static int device_scan(hipStream_t st, const In *in, uint64_t *out, uint64_t cnt)
+{
+  size_t tmp_bytes = 0;
+  HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, in, out, (uint64_t)0, cnt, rocprim::plus<uint64_t>(), st));
+  DevBuf<uint8_t> tmp;
+  HIP_TRY(tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+  HIP_TRY(rocprim::exclusive_scan((void *)tmp.p, tmp_bytes, in, out, (uint64_t)0, cnt, rocprim::plus<uint64_t>(), st));
+  HIP_TRY(hipStreamSynchronize(st));  // before tmp goes
+  return MCX_OK;
+}
+
+// The multi-word key sort of export, `sort` and unitigs: orders a permutation of m items by W key words with an LSD
+// radix sort, least significant word (W - 1) first, every pass stable.  perm[0] holds the permutation to start from
+// (iota, or the items in any order).  word(w, first, through, dst, &have) supplies word w of the items taken through
+// `through` and returns an MCX code: it fills dst, or -- on the first pass only, where `through` is still the caller's
+// own order -- sets `have` to keys it already holds.  keys[0] takes every pass's sorted keys, keys[1] is dst; tmp /
+// tmp_bytes come from sort_perm_scratch, so that every caller allocates its own way.  top_bits: bits of word 0.
+// `span`: the graph whose profile gets a "radix_sort_pairs" span per pass, or nullptr.  *out = perm[0] or perm[1],
+// whichever holds the result; nothing is synchronised.
+static int sort_perm_scratch(hipStream_t st, uint64_t m, size_t *tmp_bytes)
+{
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, *tmp_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, m, 0, 64, st));
+  return MCX_OK;
+}
+template <class WordFn>
+static int sort_perm_by_words(hipStream_t st, uint64_t m, int W, int top_bits, uint64_t *const keys[2], uint64_t *const perm[2], void *tmp,
+                              size_t tmp_bytes, mcx_graph *span, WordFn word, uint64_t **out)
+{
+  uint64_t *cur = perm[0], *nxt = perm[1];
+  for (int w = W - 1; w >= 0; w--) {
+    const uint64_t *have = nullptr;
+    int rc = word(w, w == W - 1, (const uint64_t *)cur, keys[1], &have);
+    if (rc != MCX_OK) return rc;
+    // (the caller's keys are read-only: rocprim is instantiated for const and for scratch input, as it always was here)
+    auto radix_sort_pass = [&](auto *in) {
+      SpanGuard sp(span, "radix_sort_pairs");
+      return rocprim::radix_sort_pairs(tmp, tmp_bytes, in, keys[0], cur, nxt, m, 0, w ? 64 : top_bits, st);
+    };
+    HIP_TRY(have ? radix_sort_pass(have) : radix_sort_pass(keys[1]));
+    std::swap(cur, nxt);
+  }
+  *out = cur;
+  return MCX_OK;
 }
 
 template <class K> static void allow_lds(K kernel, size_t bytes)
@@ -1590,7 +1654,8 @@ extern "C" int mcx_graph_insert_tuples_dev(mcx_graph *g, int colour, const void 
 // experiments (tools/exp_hbm_map.py): the split's write-pattern probe on any device buffer, timed
 extern "C" int mcx_debug_probe(void *d_buf, uint64_t cap_words, uint32_t nregions, uint32_t spb, uint32_t iters, uint32_t jit_mask, float *ms_out)
 {
-  hipEvent_t e0, e1;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ScopeExit drop_events([&] { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); });
   HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
   float t = 0.f;
   for (int rep = 0; rep < 2; rep++) {
@@ -1600,7 +1665,6 @@ extern "C" int mcx_debug_probe(void *d_buf, uint64_t cap_words, uint32_t nregion
     HIP_TRY(hipEventSynchronize(e1));
     HIP_TRY(hipEventElapsedTime(&t, e0, e1));
   }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   if (ms_out) *ms_out = t;
   return MCX_OK;
 }
@@ -1634,22 +1698,21 @@ extern "C" int mcx_graph_hashtest(mcx_graph *g, uint64_t first, uint64_t n)
   HIP_TRY(hipSetDevice(g->device));
   const uint64_t chunk = std::min<uint64_t>(n, 1ull << 26);  // 64 M keys = 512 MiB (W = 1) of scratch
   if (!chunk) return mcx_graph_sync(g);
-  uint64_t *d_keys = nullptr;
-  uint8_t *d_edges = nullptr;
-  if (hipMalloc((void **)&d_keys, chunk * 8 * g->W) != hipSuccess || hipMalloc((void **)&d_edges, chunk) != hipSuccess) {
-    (void)hipGetLastError(); (void)hipFree(d_keys); (void)hipFree(d_edges);
+  DevBuf<uint64_t> d_keys;
+  DevBuf<uint8_t> d_edges;
+  if (d_keys.alloc(chunk * g->W) != hipSuccess || d_edges.alloc(chunk) != hipSuccess) {
+    (void)hipGetLastError();
     return fail(MCX_ERR_NOMEM, "out of device memory for the hashtest key buffer");
   }
   int rc = MCX_OK;
   if (hipMemsetAsync(d_edges, 0, chunk, g->stream) != hipSuccess) rc = fail(MCX_ERR_HIP, "hipMemsetAsync failed");
   for (uint64_t lo = 0; lo < n && rc == MCX_OK; lo += chunk) {
     const uint64_t cnt = std::min(chunk, n - lo);
-    LAUNCH_W4(g->W, k_hashtest_keys, dim3(4096), dim3(256), 0, g->stream, d_keys, first + lo, cnt);
+    LAUNCH_W4(g->W, k_hashtest_keys, dim3(4096), dim3(256), 0, g->stream, d_keys.p, first + lo, cnt);
     rc = mcx_graph_insert_tuples_dev(g, 0, d_keys, d_edges, cnt);
     // (the binning kernel that reads the buffer runs on the same stream as the generator of the next chunk)
   }
-  const int rc2 = mcx_graph_sync(g);
-  (void)hipFree(d_keys); (void)hipFree(d_edges);
+  const int rc2 = mcx_graph_sync(g);  // (before the buffers go)
   return rc != MCX_OK ? rc : rc2;
 }
 
@@ -1660,8 +1723,8 @@ extern "C" int mcx_hashtest_func(int device, int kmer_size, uint64_t n, uint32_t
   if (kmer_size < 3 || kmer_size > 127 || !(kmer_size & 1)) return fail(MCX_ERR_ARG, "kmer size %d", kmer_size);
   if (!nparts || !hash_out) return fail(MCX_ERR_ARG, "nparts / hash_out");
   HIP_TRY(hipSetDevice(device));
-  unsigned int *d = nullptr;
-  HIP_TRY(hipMalloc((void **)&d, (size_t)nparts * 4));
+  DevBuf<unsigned int> d;
+  HIP_TRY(d.alloc(nparts));
   std::vector<unsigned int> h(nparts, 0);
   bool ok = hipMemset(d, 0, (size_t)nparts * 4) == hipSuccess;
   const int W = words_for_k(kmer_size);
@@ -1669,10 +1732,9 @@ extern "C" int mcx_hashtest_func(int device, int kmer_size, uint64_t n, uint32_t
     const uint64_t lo = (uint64_t)p * (n / nparts), hi = p + 1 == nparts ? n : lo + n / nparts;
     if (hi <= lo) continue;
     const unsigned grid = (unsigned)std::min<uint64_t>((hi - lo + 255) / 256, 8192);
-    LAUNCH_W4(W, k_hashtest_func, dim3(grid), dim3(256), 0, 0, lo, hi, d + p);
+    LAUNCH_W4(W, k_hashtest_func, dim3(grid), dim3(256), 0, 0, lo, hi, d.p + p);
   }
   ok = ok && hipMemcpy(h.data(), d, (size_t)nparts * 4, hipMemcpyDeviceToHost) == hipSuccess;
-  (void)hipFree(d);
   if (!ok) { (void)hipGetLastError(); return fail(MCX_ERR_HIP, "hashtest kernels failed"); }
   uint64_t sum = 0;
   for (uint32_t p = 0; p < nparts; p++) sum += h[p];
@@ -2659,14 +2721,12 @@ static int add_reads_must_exist(mcx_graph *g, int colour, const uint8_t *bases, 
                                 const uint64_t *off, uint64_t nreads, uint8_t fq, uint8_t hp)
 {
   const uint64_t base0 = off[0], nb = off[nreads] - off[0];
-  uint8_t *d_bases = nullptr, *d_quals = nullptr;
-  uint64_t *d_off = nullptr;
+  DevBuf<uint8_t> d_bases, d_quals;
+  DevBuf<uint64_t> d_off;
   std::vector<uint64_t> rel(nreads + 1);
   for (uint64_t i = 0; i <= nreads; i++) rel[i] = off[i] - base0;
-  auto cleanup = [&]() { (void)hipFree(d_bases); (void)hipFree(d_quals); (void)hipFree(d_off); };
-  if (hipMalloc((void **)&d_bases, nb + 16) != hipSuccess || hipMalloc((void **)&d_off, (nreads + 1) * 8) != hipSuccess ||
-      (quals && fq > 0 && hipMalloc((void **)&d_quals, nb + 16) != hipSuccess)) {
-    cleanup();
+  if (d_bases.alloc(nb + 16) != hipSuccess || d_off.alloc(nreads + 1) != hipSuccess ||
+      (quals && fq > 0 && d_quals.alloc(nb + 16) != hipSuccess)) {
     (void)hipGetLastError();
     return fail(MCX_ERR_NOMEM, "out of device memory for a read batch");
   }
@@ -2681,7 +2741,6 @@ static int add_reads_must_exist(mcx_graph *g, int colour, const uint8_t *bases, 
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(g->stream));
-  cleanup();
   return MCX_OK;
 }
 
@@ -2732,25 +2791,11 @@ struct CutJob {  // one batch of whole reads on one device
   mcx_graph *g = nullptr;
   uint64_t nreads = 0, nunits = 0, nb = 0;
   uint32_t pmask = 0, fq1 = 0, fq2 = 0, hp = 0;
-  uint8_t *d_bases = nullptr, *d_quals = nullptr, *d_keep = nullptr;
-  uint64_t *d_off = nullptr, *d_node = nullptr;
-  unsigned long long *d_ndup = nullptr;
-  CutJob() = default;
-  CutJob(const CutJob &) = delete;
-  CutJob &operator=(const CutJob &) = delete;
-  ~CutJob()
-  {
-    if (!g) return;
-    (void)hipSetDevice(g->device);
-    (void)hipFree(d_bases); (void)hipFree(d_quals); (void)hipFree(d_keep); (void)hipFree(d_off); (void)hipFree(d_node); (void)hipFree(d_ndup);
-  }
+  DevBuf<uint8_t> d_bases, d_quals, d_keep;
+  DevBuf<uint64_t> d_off, d_node;
+  DevBuf<unsigned long long> d_ndup;
+  ~CutJob() { if (g) (void)hipSetDevice(g->device); }  // (runs before the members free themselves)
 };
-#define CUT_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess)                                                                 \
-      return fail(_e == hipErrorOutOfMemory ? MCX_ERR_NOMEM : MCX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
 
 // reads -> device (asynchronous on the handle's stream); mates turned to FF when the filter runs
 static int cut_upload(CutJob &J, mcx_graph *g, const uint8_t *bases, const uint8_t *quals, const uint64_t *off, uint64_t nreads,
@@ -2762,27 +2807,27 @@ static int cut_upload(CutJob &J, mcx_graph *g, const uint8_t *bases, const uint8
   J.pmask = paired ? 1u : 0u; J.fq1 = fq1; J.fq2 = fq2; J.hp = hp;
   const uint64_t base0 = off[0];
   J.nb = off[nreads] - off[0];
-  CUT_TRY(hipSetDevice(g->device));
+  HIP_TRY(hipSetDevice(g->device));
   std::vector<uint64_t> rel(nreads + 1);
   for (uint64_t i = 0; i <= nreads; i++) rel[i] = off[i] - base0;
   const bool use_q = quals && (fq1 > 0 || fq2 > 0);
-  CUT_TRY(hipMalloc((void **)&J.d_bases, J.nb + 16));
-  if (use_q) CUT_TRY(hipMalloc((void **)&J.d_quals, J.nb + 16));
-  CUT_TRY(hipMalloc((void **)&J.d_off, (nreads + 1) * 8));
+  HIP_TRY(J.d_bases.alloc(J.nb + 16));
+  if (use_q) HIP_TRY(J.d_quals.alloc(J.nb + 16));
+  HIP_TRY(J.d_off.alloc(nreads + 1));
   if (filter) {
-    CUT_TRY(hipMalloc((void **)&J.d_node, nreads * 8));
-    CUT_TRY(hipMalloc((void **)&J.d_keep, nreads));
-    CUT_TRY(hipMalloc((void **)&J.d_ndup, 8));
-    CUT_TRY(hipMemsetAsync(J.d_ndup, 0, 8, g->stream));
+    HIP_TRY(J.d_node.alloc(nreads));
+    HIP_TRY(J.d_keep.alloc(nreads));
+    HIP_TRY(J.d_ndup.alloc(1));
+    HIP_TRY(hipMemsetAsync(J.d_ndup, 0, 8, g->stream));
   }
-  CUT_TRY(hipMemcpyAsync(J.d_bases, bases + base0, J.nb, hipMemcpyHostToDevice, g->stream));
-  if (J.d_quals) CUT_TRY(hipMemcpyAsync(J.d_quals, quals + base0, J.nb, hipMemcpyHostToDevice, g->stream));
-  CUT_TRY(hipMemcpyAsync(J.d_off, rel.data(), (nreads + 1) * 8, hipMemcpyHostToDevice, g->stream));
-  CUT_TRY(hipStreamSynchronize(g->stream));  // `rel` is a local
+  HIP_TRY(hipMemcpyAsync(J.d_bases, bases + base0, J.nb, hipMemcpyHostToDevice, g->stream));
+  if (J.d_quals) HIP_TRY(hipMemcpyAsync(J.d_quals, quals + base0, J.nb, hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipMemcpyAsync(J.d_off, rel.data(), (nreads + 1) * 8, hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));  // `rel` is a local
   const unsigned blocks = (unsigned)((nreads + 127) / 128);
   if (filter && matedir)
     hipLaunchKernelGGL(k_pcr_orient, dim3(blocks), dim3(128), 0, g->stream, J.d_bases, J.d_quals, (const uint64_t *)J.d_off, nreads, J.pmask, (uint32_t)matedir);
-  CUT_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MCX_OK;
 }
 
@@ -2790,18 +2835,18 @@ static int cut_upload(CutJob &J, mcx_graph *g, const uint8_t *bases, const uint8
 static int cut_starts(CutJob &J)
 {
   mcx_graph *g = J.g;
-  CUT_TRY(hipSetDevice(g->device));
+  HIP_TRY(hipSetDevice(g->device));
   if (!g->d_readstrt) {  // 2 x u32 per slot, only ever allocated for --remove-pcr
     if (hipMalloc((void **)&g->d_readstrt, g->t.nslots * 8) != hipSuccess) {
       (void)hipGetLastError();
       return fail(MCX_ERR_NOMEM, "out of device memory for the read-start table");
     }
-    CUT_TRY(hipMemsetAsync(g->d_readstrt, 0xff, g->t.nslots * 8, g->stream));
+    HIP_TRY(hipMemsetAsync(g->d_readstrt, 0xff, g->t.nslots * 8, g->stream));
   }
   const unsigned blocks = (unsigned)((J.nreads + 127) / 128);
   LAUNCH_W4(g->W, k_pcr_starts, dim3(blocks), dim3(128), 0, g->stream, g->t, (const uint8_t *)J.d_bases, (const uint8_t *)J.d_quals,
             (const uint64_t *)J.d_off, J.nreads, g->k, J.fq1, J.fq2, J.pmask, J.hp, g->d_readstrt, J.d_node, g->d_ctr, owner_spec(g));
-  CUT_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return MCX_OK;
 }
 
@@ -2810,40 +2855,37 @@ static int cut_starts(CutJob &J)
 static int cut_finish(CutJob &J, int colour)
 {
   mcx_graph *g = J.g;
-  CUT_TRY(hipSetDevice(g->device));
+  HIP_TRY(hipSetDevice(g->device));
   const uint64_t nreads = J.nreads;
   const unsigned blocks = (unsigned)((nreads + 127) / 128);
   DevBuf<uint64_t> d_sizes, d_ooff;
-  DevBuf<uint8_t> d_out, d_tmp;
-  size_t tmp_bytes = 0;
-  CUT_TRY(d_sizes.alloc(nreads + 1));
-  CUT_TRY(d_ooff.alloc(nreads + 1));
-  CUT_TRY(hipMemsetAsync(d_sizes, 0, (nreads + 1) * 8, g->stream));
+  DevBuf<uint8_t> d_out;
+  HIP_TRY(d_sizes.alloc(nreads + 1));
+  HIP_TRY(d_ooff.alloc(nreads + 1));
+  HIP_TRY(hipMemsetAsync(d_sizes, 0, (nreads + 1) * 8, g->stream));
   hipLaunchKernelGGL(k_qh_contigs, dim3(blocks), dim3(128), 0, g->stream, (const uint8_t *)J.d_bases, (const uint8_t *)J.d_quals,
                      (const uint64_t *)J.d_off, nreads, g->k, J.fq1, J.fq2, J.pmask, J.hp, (const uint8_t *)J.d_keep, 0, d_sizes.p,
                      (const uint64_t *)nullptr, (uint8_t *)nullptr);
-  CUT_TRY(hipGetLastError());
-  CUT_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, d_sizes.p, d_ooff.p, (uint64_t)0, nreads + 1, rocprim::plus<uint64_t>(), g->stream));
-  CUT_TRY(d_tmp.alloc(tmp_bytes ? tmp_bytes : 16));
-  CUT_TRY(rocprim::exclusive_scan((void *)d_tmp.p, tmp_bytes, d_sizes.p, d_ooff.p, (uint64_t)0, nreads + 1, rocprim::plus<uint64_t>(), g->stream));
+  HIP_TRY(hipGetLastError());
+  int rc = device_scan(g->stream, (const uint64_t *)d_sizes.p, d_ooff.p, nreads + 1);
+  if (rc != MCX_OK) return rc;
   uint64_t out_bytes = 0;
-  CUT_TRY(hipMemcpyAsync(&out_bytes, d_ooff.p + nreads, 8, hipMemcpyDeviceToHost, g->stream));
-  CUT_TRY(hipStreamSynchronize(g->stream));
-  int rc = MCX_OK;
+  HIP_TRY(hipMemcpyAsync(&out_bytes, d_ooff.p + nreads, 8, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   if (out_bytes) {
-    CUT_TRY(d_out.alloc(out_bytes + 64));
-    CUT_TRY(hipMemsetAsync(d_out.p + out_bytes, '\n', 64, g->stream));
+    HIP_TRY(d_out.alloc(out_bytes + 64));
+    HIP_TRY(hipMemsetAsync(d_out.p + out_bytes, '\n', 64, g->stream));
     hipLaunchKernelGGL(k_qh_contigs, dim3(blocks), dim3(128), 0, g->stream, (const uint8_t *)J.d_bases, (const uint8_t *)J.d_quals,
                        (const uint64_t *)J.d_off, nreads, g->k, J.fq1, J.fq2, J.pmask, J.hp, (const uint8_t *)J.d_keep, 1, d_sizes.p,
                        (const uint64_t *)d_ooff.p, d_out.p);
-    CUT_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     StreamLaunch SL{d_out.p, out_bytes, 0, out_bytes, nullptr};
     rc = submit_stream(g, SL, colour);
-    CUT_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipSetDevice(g->device));
   }
   hipLaunchKernelGGL(k_count_sizes, dim3(256), dim3(256), 0, g->stream, (const uint64_t *)d_sizes.p, (const uint8_t *)J.d_keep, nreads, g->d_ctr);
-  CUT_TRY(hipGetLastError());
-  CUT_TRY(hipStreamSynchronize(g->stream));  // d_out is read by the kernels submit_stream launched
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(g->stream));  // d_out is read by the kernels submit_stream launched
   return rc;
 }
 
@@ -2863,8 +2905,8 @@ static int add_reads_cut(mcx_graph *g, int colour, const uint8_t *bases, const u
     hipLaunchKernelGGL(k_pcr_decide, dim3(ublocks), dim3(256), 0, g->stream, (const uint64_t *)J.d_node, (const uint32_t *)g->d_readstrt,
                        J.nunits, J.pmask, J.d_keep, J.d_ndup);
     hipLaunchKernelGGL(k_pcr_commit, dim3(blocks), dim3(128), 0, g->stream, (const uint64_t *)J.d_node, nreads, g->d_readstrt);
-    CUT_TRY(hipGetLastError());
-    CUT_TRY(hipMemcpyAsync(&h_ndup, J.d_ndup, 8, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&h_ndup, J.d_ndup, 8, hipMemcpyDeviceToHost, g->stream));
   }
   rc = cut_finish(J, colour);  // (synchronises the stream: h_ndup has arrived)
   if (ndup) *ndup = h_ndup;
@@ -3879,17 +3921,6 @@ struct UnWork {
   DevBuf<uint64_t> uoff, eoff;
 };
 
-template <class In> static int un_scan(mcx_graph *g, const In *in, uint64_t *out, uint64_t cnt)
-{
-  size_t tmp_bytes = 0;
-  HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, in, out, (uint64_t)0, cnt, rocprim::plus<uint64_t>(), g->stream));
-  DevBuf<uint8_t> tmp;
-  HIP_TRY(tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
-  HIP_TRY(rocprim::exclusive_scan((void *)tmp.p, tmp_bytes, in, out, (uint64_t)0, cnt, rocprim::plus<uint64_t>(), g->stream));
-  HIP_TRY(hipStreamSynchronize(g->stream));  // before tmp goes
-  return MCX_OK;
-}
-
 // pointer jumping until a round finishes no node
 static int un_jump(mcx_graph *g, uint64_t m, const uint32_t *list, const uint8_t *lk, uint64_t *pk, uint32_t *d_changed)
 {
@@ -3964,20 +3995,18 @@ static int unitigs_prepare(mcx_graph *g, int fmt, UnWork &w)
   HIP_TRY(ks.alloc(nu));
   HIP_TRY(ks2.alloc(nu));
   {
-    // LSD over the key words, least significant first, every pass stable (the sorted export's multi-word sort)
     size_t tmp_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, nu, 0, 64, st));
+    if ((rc = sort_perm_scratch(st, nu, &tmp_bytes)) != MCX_OK) return rc;
     DevBuf<uint8_t> tmp;
     HIP_TRY(tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
-    uint64_t *cur = starts.p, *nxt = sorted.p;
-    for (int wd = g->W - 1; wd >= 0; wd--) {
-      GRID_LAUNCH(k_un_keyword, nu, g->t, nu, (const uint64_t *)c->slot_of.p, (const uint64_t *)cur, (uint32_t)wd, ks.p);
-      SpanGuard sp(g, "radix_sort_pairs");
-      HIP_TRY(rocprim::radix_sort_pairs((void *)tmp.p, tmp_bytes, ks.p, ks2.p, cur, nxt, nu, 0, wd ? 64 : 2 * g->k - 64 * (g->W - 1), st));
-      std::swap(cur, nxt);
-    }
+    uint64_t *const keys[2] = {ks2.p, ks.p}, *const perm[2] = {starts.p, sorted.p}, *res = nullptr;
+    auto word = [&](int wd, bool, const uint64_t *through, uint64_t *dst, const uint64_t **) -> int {
+      GRID_LAUNCH(k_un_keyword, nu, g->t, nu, (const uint64_t *)c->slot_of.p, through, (uint32_t)wd, dst);
+      return MCX_OK;
+    };
+    if ((rc = sort_perm_by_words(st, nu, g->W, 2 * g->k - 64 * (g->W - 1), keys, perm, tmp.p, tmp_bytes, g, word, &res)) != MCX_OK) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    if (cur != sorted.p) std::swap(starts.p, sorted.p);  // sorted = the permutation after the last pass
+    if (res != sorted.p) std::swap(starts.p, sorted.p);  // sorted = the permutation after the last pass
   }
   HIP_TRY(unum.alloc(n));
   HIP_TRY(hipMemsetAsync(unum, 0, n * 4, st));
@@ -3990,12 +4019,12 @@ static int unitigs_prepare(mcx_graph *g, int fmt, UnWork &w)
   HIP_TRY(hipMemsetAsync(w.uoff.p + nu, 0, 8, st));
   GRID_LAUNCH(k_un_number, nu, nu, tfmt, g->k, (const uint64_t *)sorted.p, (const uint32_t *)c->uid.p, (const uint32_t *)c->len.p, (const uint32_t *)head.p,
               (const uint64_t *)pk.p, (const uint8_t *)c->ue.p, unum.p, w.ufirst.p, w.ulast.p, w.ulen.p, w.upn.p, w.uoff.p);
-  if ((rc = un_scan(g, (const uint64_t *)w.uoff.p, w.uoff.p, nu + 1)) != MCX_OK) return rc;
+  if ((rc = device_scan(st, (const uint64_t *)w.uoff.p, w.uoff.p, nu + 1)) != MCX_OK) return rc;
   {
     // positions in the base array: fewer than 2^31 k-mers, so 32 bits hold them (scanned in 64, narrowed by ks)
     DevBuf<uint64_t> b64;
     HIP_TRY(b64.alloc(nu + 1));
-    if ((rc = un_scan(g, (const uint32_t *)w.ulen.p, b64.p, nu)) != MCX_OK) return rc;
+    if ((rc = device_scan(st, (const uint32_t *)w.ulen.p, b64.p, nu)) != MCX_OK) return rc;
     GRID_LAUNCH(k_un_narrow, nu, nu, (const uint64_t *)b64.p, w.ubase.p);
     HIP_TRY(hipStreamSynchronize(st));
   }
@@ -4015,7 +4044,7 @@ static int unitigs_prepare(mcx_graph *g, int fmt, UnWork &w)
     GRID_LAUNCH_W(k_un_edges, 2 * nu, g->t, g->k, fmt, nu, (const uint64_t *)c->slot_of.p, (const uint32_t *)c->map.p, (const uint8_t *)c->ue.p,
                   (const uint32_t *)w.ufirst.p, (const uint32_t *)w.ulast.p, (const uint32_t *)w.kun.p, (const uint32_t *)w.krk.p,
                   (const uint8_t *)w.kori.p, w.etgt.p, elen.p);
-    if ((rc = un_scan(g, (const uint8_t *)elen.p, w.eoff.p, 8 * nu + 1)) != MCX_OK) return rc;
+    if ((rc = device_scan(st, (const uint8_t *)elen.p, w.eoff.p, 8 * nu + 1)) != MCX_OK) return rc;
     HIP_TRY(hipMemcpyAsync(&w.edge_bytes, w.eoff.p + 8 * nu, 8, hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipStreamSynchronize(st));  // before the scratch of this function goes
@@ -4163,11 +4192,6 @@ static int export_t(mcx_graph *g, int sorted, mcx_sink_fn sink, void *ctx)
       return fail(MCX_ERR_NOMEM, "not enough free HBM to dump the graph (%llu MB free)", (unsigned long long)(avail >> 20));
   }
 
-  hipEvent_t done[2] = {nullptr, nullptr};
-  uint8_t *d_rec2[2] = {nullptr, nullptr}, *h_rec2[2] = {nullptr, nullptr};
-  unsigned long long *d_cursor = nullptr;
-  uint64_t *d_k0 = nullptr, *d_k1 = nullptr, *d_slot = nullptr, *d_idx = nullptr, *d_idx2 = nullptr, *d_ks = nullptr, *d_ks2 = nullptr;
-  void *d_tmp = nullptr;
   // Scratch arrays come out of the partition workspace when the graph has one and it is empty (after the closing flush
   // it is: 18-65 GB of HBM with nothing in it) -- a bump allocator over it instead of seven hipMalloc / hipFree of
   // gigabytes each: 40 ms of an export on a good day, 200+ ms when the driver has to hand over memory another process
@@ -4176,64 +4200,56 @@ static int export_t(mcx_graph *g, int sorted, mcx_sink_fn sink, void *ctx)
   // (two pools: the region bins and the sub-table bins.  The command's 2.1 G-occurrence window gives 18.5 + 2.9 GB; C2's
   // 337 M k-mers need 5 x 2.7 GB of arrays + 5.4 GB for the radix sort, and the one array that found no room made a
   // hipMalloc of 150 ms inside the bench process)
+  struct Pool {
+    uint8_t *base[2];
+    uint64_t bytes[2], off[2];
+    std::vector<void *> owned;  // what found no room and was hipMalloc'd
+    ~Pool() { reset(); }
+    hipError_t alloc(void **p, size_t want)
+    {
+      const uint64_t need = ((uint64_t)want + 255) & ~255ull;
+      for (int i = 0; i < 2; i++)
+        if (base[i] && off[i] + need <= bytes[i]) { *p = base[i] + off[i]; off[i] += need; return hipSuccess; }
+      const double t0 = now_s();
+      const hipError_t e = hipMalloc(p, want);
+      if (e == hipSuccess) owned.push_back(*p);
+      if (getenv("MCX_TIMING")) fprintf(stderr, "[timing]   export: %.2f GB of scratch found no room in the idle bins (%.1f + %.1f GB): hipMalloc %.1f ms\n", want / 1e9,
+                                        bytes[0] / 1e9, bytes[1] / 1e9, (now_s() - t0) * 1e3);
+      return e;
+    }
+    void reset()  // everything handed out is void after this
+    {
+      for (void *q : owned) (void)hipFree(q);
+      owned.clear();
+      off[0] = off[1] = 0;
+    }
+  };
   const bool bins_idle = g->l1_keys && !g->pending && !g->pending_l2;
-  uint8_t *pool[2] = {bins_idle ? reinterpret_cast<uint8_t *>(g->l1_keys) : nullptr, bins_idle ? reinterpret_cast<uint8_t *>(g->l2_keys) : nullptr};
-  const uint64_t pool_bytes[2] = {pool[0] ? (uint64_t)g->nsets * g->b1 * g->rep1 * g->cap1 * 8 * g->W : 0,
-                                  pool[1] ? (uint64_t)(g->l2_hi ? g->l2_regions / 2 : g->l2_regions) * g->subs_per_bin * g->cap2 * 8 * g->W : 0};  // (placed bins: the first half's allocation)
-  uint64_t pool_off[2] = {0, 0};
-  std::vector<void *> owned;
-  auto salloc = [&](void **p, size_t bytes) -> hipError_t {
-    const uint64_t need = ((uint64_t)bytes + 255) & ~255ull;
-    for (int i = 0; i < 2; i++)
-      if (pool[i] && pool_off[i] + need <= pool_bytes[i]) { *p = pool[i] + pool_off[i]; pool_off[i] += need; return hipSuccess; }
-    const double t0 = now_s();
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) owned.push_back(*p);
-    if (getenv("MCX_TIMING")) fprintf(stderr, "[timing]   export: %.2f GB of scratch found no room in the idle bins (%.1f + %.1f GB): hipMalloc %.1f ms\n", bytes / 1e9,
-                                      pool_bytes[0] / 1e9, pool_bytes[1] / 1e9, (now_s() - t0) * 1e3);
-    return e;
-  };
-  auto free_range = [&]() {
-    for (void *q : owned) (void)hipFree(q);
-    owned.clear();
-    pool_off[0] = pool_off[1] = 0;
-    d_k0 = d_k1 = d_slot = d_idx = d_idx2 = d_ks = d_ks2 = nullptr; d_tmp = nullptr;
-  };
+  Pool pool{{bins_idle ? reinterpret_cast<uint8_t *>(g->l1_keys) : nullptr, bins_idle ? reinterpret_cast<uint8_t *>(g->l2_keys) : nullptr}, {0, 0}, {0, 0}, {}};
+  if (pool.base[0]) pool.bytes[0] = (uint64_t)g->nsets * g->b1 * g->rep1 * g->cap1 * 8 * g->W;
+  if (pool.base[1]) pool.bytes[1] = (uint64_t)(g->l2_hi ? g->l2_regions / 2 : g->l2_regions) * g->subs_per_bin * g->cap2 * 8 * g->W;  // (placed bins: the first half's allocation)
+  export_clock("counters fetched");
+  DevBuf<unsigned long long> d_cursor;
+  HIP_TRY(d_cursor.alloc(1));
+  // records are produced and copied to pinned memory in 64 MiB chunks, double buffered: while the
+  // sink consumes chunk i on the host, the device emits and copies chunk i + 1.
   // The chunk buffers: the host entry's staging pairs when the graph has them (pinned host + device memory that sits
   // idle once the reads are in: the device is idle here, fetch_counters has just returned) -- page-locking two fresh
   // 64 MiB buffers took 23 ms on a good day and 263 ms on a bad one (`export ... buffers allocated`, round 5).
   const bool borrow = g->stage_alloc >= chunk * recsz && g->h_stage[0] && g->h_stage[1] && g->d_stage[0] && g->d_stage[1];
-  auto cleanup = [&]() {
-    free_range();
-    (void)hipFree(d_cursor);
-    for (int i = 0; i < 2; i++) {
-      if (done[i]) (void)hipEventDestroy(done[i]);
-      if (borrow) continue;
-      (void)hipFree(d_rec2[i]);
-      if (h_rec2[i]) (void)hipHostFree(h_rec2[i]);
-    }
-  };
-#define EXP_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess) {                                                               \
-      cleanup();                                                                          \
-      return fail(_e == hipErrorOutOfMemory ? MCX_ERR_NOMEM : MCX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
-    }                                                                                     \
-  } while (0)
-  export_clock("counters fetched");
-  EXP_TRY(hipMalloc((void **)&d_cursor, 8));
-  // records are produced and copied to pinned memory in 64 MiB chunks, double buffered: while the
-  // sink consumes chunk i on the host, the device emits and copies chunk i + 1
+  DevBuf<uint8_t> d_rec2[2];
+  HostBuf<uint8_t> h_rec2[2];
+  hipEvent_t done[2] = {nullptr, nullptr};
+  ScopeExit drop_events([&] { for (hipEvent_t e : done) if (e) (void)hipEventDestroy(e); });
   for (int i = 0; i < 2; i++) {
     if (borrow) {
-      d_rec2[i] = g->d_stage[i];
-      h_rec2[i] = g->h_stage[i];
+      d_rec2[i].borrow(g->d_stage[i]);
+      h_rec2[i].borrow(g->h_stage[i]);
     } else {
-      EXP_TRY(hipMalloc((void **)&d_rec2[i], chunk * recsz));
-      EXP_TRY(hipHostMalloc((void **)&h_rec2[i], chunk * recsz, hipHostMallocDefault));
+      HIP_TRY(d_rec2[i].alloc(chunk * recsz));
+      HIP_TRY(h_rec2[i].alloc(chunk * recsz));
     }
-    EXP_TRY(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
   }
   export_clock("buffers allocated");
 
@@ -4245,84 +4261,74 @@ static int export_t(mcx_graph *g, int sorted, mcx_sink_fn sink, void *ctx)
     const Range r = todo.back();
     todo.pop_back();
     const uint64_t cap = r.bits == 0 ? n : std::min<uint64_t>(n, (n >> r.bits) * 5 / 4 + 65536);
-    EXP_TRY(salloc((void **)&d_k0, cap * 8));
-    if (W == 2) EXP_TRY(salloc((void **)&d_k1, cap * 8));
-    EXP_TRY(salloc((void **)&d_slot, cap * 8));
-    EXP_TRY(hipMemsetAsync(d_cursor, 0, 8, st));
-    hipLaunchKernelGGL((k_compact<W>), dim3(g->grid), dim3(kThreads), 0, st, g->t, d_k0, d_k1, d_slot, d_cursor, cap, g->k, r.prefix, r.bits);
-    EXP_TRY(hipGetLastError());
+    uint64_t *d_k0 = nullptr, *d_k1 = nullptr, *d_slot = nullptr, *d_idx = nullptr, *d_idx2 = nullptr, *d_ks = nullptr, *d_ks2 = nullptr;
+    void *d_tmp = nullptr;
+    ScopeExit range_done([&] { pool.reset(); });
+    HIP_TRY(pool.alloc((void **)&d_k0, cap * 8));
+    if (W == 2) HIP_TRY(pool.alloc((void **)&d_k1, cap * 8));
+    HIP_TRY(pool.alloc((void **)&d_slot, cap * 8));
+    HIP_TRY(hipMemsetAsync(d_cursor, 0, 8, st));
+    hipLaunchKernelGGL((k_compact<W>), dim3(g->grid), dim3(kThreads), 0, st, g->t, d_k0, d_k1, d_slot, d_cursor.p, cap, g->k, r.prefix, r.bits);
+    HIP_TRY(hipGetLastError());
     unsigned long long found = 0;
-    EXP_TRY(hipMemcpyAsync(&found, d_cursor, 8, hipMemcpyDeviceToHost, st));
-    EXP_TRY(hipStreamSynchronize(st));
-    if (r.bits == 0 && found != n) { cleanup(); return fail(MCX_ERR_HIP, "table scan found %llu nodes, counter says %llu", found, (unsigned long long)n); }
+    HIP_TRY(hipMemcpyAsync(&found, d_cursor, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (r.bits == 0 && found != n) return fail(MCX_ERR_HIP, "table scan found %llu nodes, counter says %llu", found, (unsigned long long)n);
     if (found > cap) {  // fuller than expected: two halves, the lower one first
-      free_range();
-      if ((int)r.bits + 1 > 2 * g->k || r.bits >= 30) { cleanup(); return fail(MCX_ERR_NOMEM, "not enough free HBM to dump the graph"); }
+      if ((int)r.bits + 1 > 2 * g->k || r.bits >= 30) return fail(MCX_ERR_NOMEM, "not enough free HBM to dump the graph");
       todo.push_back({r.prefix * 2 + 1, r.bits + 1});
       todo.push_back({r.prefix * 2, r.bits + 1});
       continue;
     }
     const uint64_t m = found;
-    if (m == 0) { free_range(); continue; }
+    if (m == 0) continue;
     export_clock("compacted");
     // permutation of the compacted entries: by key (sorted) or by slot (table order)
-    size_t tmp_bytes = 0;
-    const uint64_t *first_key = sorted ? (W == 2 ? d_k1 : d_k0) : d_slot;  // (W > 2: a throw-away pass, see below)
     // (the sort's own temporary first: it is the largest block -- two more arrays of m words -- and the bump allocator
     // fills the first pool in order; the smaller arrays find room in what is left or in the second pool)
-    EXP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, first_key, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, m, 0, 64, st));
-    EXP_TRY(salloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
-    EXP_TRY(salloc((void **)&d_idx, m * 8));
-    EXP_TRY(salloc((void **)&d_idx2, m * 8));
-    EXP_TRY(salloc((void **)&d_ks, m * 8));
-    if (sorted && W >= 2) EXP_TRY(salloc((void **)&d_ks2, m * 8));
+    size_t tmp_bytes = 0;
+    if ((rc = sort_perm_scratch(st, m, &tmp_bytes)) != MCX_OK) return rc;
+    HIP_TRY(pool.alloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
+    HIP_TRY(pool.alloc((void **)&d_idx, m * 8));
+    HIP_TRY(pool.alloc((void **)&d_idx2, m * 8));
+    HIP_TRY(pool.alloc((void **)&d_ks, m * 8));
+    if (sorted && W >= 2) HIP_TRY(pool.alloc((void **)&d_ks2, m * 8));
     const unsigned gb = (unsigned)((m + 255) / 256);
     hipLaunchKernelGGL(k_iota, dim3(gb), dim3(256), 0, st, d_idx, m);
-    EXP_TRY(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, first_key, d_ks, d_idx, d_idx2, m, 0, 64, st));
-    uint64_t *perm = d_idx2;
-    if (sorted && W == 2) {  // LSD: stable second pass on the most significant word
-      hipLaunchKernelGGL(k_gather_u64, dim3(gb), dim3(256), 0, st, (const uint64_t *)d_k0, (const uint64_t *)d_idx2, d_ks2, m);
-      EXP_TRY(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_ks2, d_ks, d_idx2, d_idx, m, 0, 64, st));
-      perm = d_idx;
-    }
-    if (sorted && W > 2) {
-      // k > 63: the pass above ordered by the top word only (d_k0).  Redo as an LSD sort over all W words, least
-      // significant first, every pass stable; a pass fetches its word from the table through the permutation so far.
-      hipLaunchKernelGGL(k_iota, dim3(gb), dim3(256), 0, st, d_idx, m);
-      uint64_t *cur = d_idx, *nxt = d_idx2;
-      for (int w = W - 1; w >= 0; w--) {
-        hipLaunchKernelGGL(k_gather_keyword, dim3(gb), dim3(256), 0, st, g->t, (const uint64_t *)d_slot, (const uint64_t *)cur, (uint32_t)w, d_ks2, m);
-        EXP_TRY(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_ks2, d_ks, cur, nxt, m, 0, 64, st));
-        std::swap(cur, nxt);
-      }
-      perm = cur;
-    }
-    EXP_TRY(hipStreamSynchronize(st));
+    // table order: the slot is the one "word".  Sorted: k_compact left the words of one- and two-word keys in d_k0 /
+    // d_k1; longer keys (k > 63) are fetched from the table, a word per pass.
+    auto word = [&](int w, bool first, const uint64_t *through, uint64_t *dst, const uint64_t **have) -> int {
+      if (!sorted) *have = d_slot;
+      else if (W <= 2 && first) *have = W == 2 ? d_k1 : d_k0;
+      else if (W == 2) hipLaunchKernelGGL(k_gather_u64, dim3(gb), dim3(256), 0, st, (const uint64_t *)d_k0, through, dst, m);
+      else GRID_LAUNCH(k_un_keyword, m, g->t, m, (const uint64_t *)d_slot, through, (uint32_t)w, dst);
+      return MCX_OK;
+    };
+    uint64_t *const keys[2] = {d_ks, d_ks2}, *const perms[2] = {d_idx, d_idx2}, *perm = nullptr;
+    if ((rc = sort_perm_by_words(st, m, sorted ? W : 1, 64, keys, perms, d_tmp, tmp_bytes, nullptr, word, &perm)) != MCX_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
     export_clock("sorted");
     auto produce = [&](uint64_t first, int b) -> hipError_t {
       const uint64_t cnt = std::min(chunk, m - first);
       hipLaunchKernelGGL((k_emit_records<W>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, g->t,
-                         (const uint64_t *)d_slot, (const uint64_t *)perm, first, cnt, (uint32_t)g->ncols_vis, d_rec2[b]);
+                         (const uint64_t *)d_slot, (const uint64_t *)perm, first, cnt, (uint32_t)g->ncols_vis, d_rec2[b].p);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
       e = hipMemcpyAsync(h_rec2[b], d_rec2[b], cnt * recsz, hipMemcpyDeviceToHost, st);
       if (e != hipSuccess) return e;
       return hipEventRecord(done[b], st);
     };
-    EXP_TRY(produce(0, 0));
+    HIP_TRY(produce(0, 0));
     int b = 0;
     for (uint64_t first = 0; first < m; first += chunk, b ^= 1) {
       const uint64_t cnt = std::min(chunk, m - first);
-      if (first + chunk < m) EXP_TRY(produce(first + chunk, b ^ 1));
-      EXP_TRY(hipEventSynchronize(done[b]));
-      if (sink(ctx, h_rec2[b], cnt * recsz) != 0) { cleanup(); return fail(MCX_ERR_SINK, "export sink failed"); }
+      if (first + chunk < m) HIP_TRY(produce(first + chunk, b ^ 1));
+      HIP_TRY(hipEventSynchronize(done[b]));
+      if (sink(ctx, h_rec2[b], cnt * recsz) != 0) return fail(MCX_ERR_SINK, "export sink failed");
     }
     emitted += m;
-    free_range();
   }
   export_clock("records delivered");
-#undef EXP_TRY
-  cleanup();
   if (emitted != n) return fail(MCX_ERR_HIP, "export delivered %llu of %llu nodes", (unsigned long long)emitted, (unsigned long long)n);
   return MCX_OK;
 }
@@ -4442,19 +4448,18 @@ extern "C" int mcx_ubench_stream(int device, uint64_t bytes, double *copy_gbs, d
   HIP_TRY(hipSetDevice(device));
   const uint64_t n = bytes / 16;
   if (n < (1u << 20)) return fail(MCX_ERR_ARG, "buffers of at least 16 MiB");
-  ulonglong2 *a = nullptr, *b = nullptr;
-  unsigned long long *sink = nullptr;
-  if (hipMalloc((void **)&a, n * 16) != hipSuccess || hipMalloc((void **)&b, n * 16) != hipSuccess || hipMalloc((void **)&sink, 8) != hipSuccess) {
-    (void)hipGetLastError(); (void)hipFree(a); (void)hipFree(b); (void)hipFree(sink);
+  DevBuf<ulonglong2> a, b;
+  DevBuf<unsigned long long> sink;
+  if (a.alloc(n) != hipSuccess || b.alloc(n) != hipSuccess || sink.alloc(1) != hipSuccess) {
+    (void)hipGetLastError();
     return fail(MCX_ERR_NOMEM, "out of device memory for the streaming microbenchmark");
   }
   (void)hipMemset(a, 1, n * 16); (void)hipMemset(b, 2, n * 16);
   const int grid = 8192;
   double ms[3] = {0, 0, 0};
-  int rc = ubench_time([&] { k_ubench_stream<0, 8><<<grid, 256>>>(a, b, n, sink); }, 5, &ms[0]);
-  if (!rc) rc = ubench_time([&] { k_ubench_stream<1, 8><<<grid, 256>>>(a, b, n, sink); }, 5, &ms[1]);
-  if (!rc) rc = ubench_time([&] { k_ubench_stream<2, 8><<<grid, 256>>>(a, b, n, sink); }, 5, &ms[2]);
-  (void)hipFree(a); (void)hipFree(b); (void)hipFree(sink);
+  int rc = ubench_time([&] { k_ubench_stream<0, 8><<<grid, 256>>>(a.p, b.p, n, sink.p); }, 5, &ms[0]);
+  if (!rc) rc = ubench_time([&] { k_ubench_stream<1, 8><<<grid, 256>>>(a.p, b.p, n, sink.p); }, 5, &ms[1]);
+  if (!rc) rc = ubench_time([&] { k_ubench_stream<2, 8><<<grid, 256>>>(a.p, b.p, n, sink.p); }, 5, &ms[2]);
   if (rc) return fail(MCX_ERR_HIP, "streaming microbenchmark failed");
   if (copy_gbs) *copy_gbs = 2.0 * n * 16 / ms[0] / 1e6;
   if (read_gbs) *read_gbs = 1.0 * n * 16 / ms[1] / 1e6;
@@ -4470,19 +4475,18 @@ extern "C" int mcx_ubench_random_rmw(int device, uint64_t table_bytes, uint64_t 
   HIP_TRY(hipSetDevice(device));
   const uint64_t nrec = table_bytes / 16;
   if (nrec < 1024 || nupdates < (1u << 20)) return fail(MCX_ERR_ARG, "table of at least 16 KiB, at least 1 M updates");
-  uint64_t *tab = nullptr;
-  unsigned long long *sink = nullptr;
-  if (hipMalloc((void **)&tab, nrec * 16) != hipSuccess || hipMalloc((void **)&sink, 8) != hipSuccess) {
-    (void)hipGetLastError(); (void)hipFree(tab); (void)hipFree(sink);
+  DevBuf<uint64_t> tab;
+  DevBuf<unsigned long long> sink;
+  if (tab.alloc(nrec * 2) != hipSuccess || sink.alloc(1) != hipSuccess) {
+    (void)hipGetLastError();
     return fail(MCX_ERR_NOMEM, "out of device memory for the random-access microbenchmark");
   }
   (void)hipMemset(tab, 0, nrec * 16);
   double ms[3] = {0, 0, 0};
   uint64_t seed = 7;
-  int rc = ubench_time([&] { k_ubench_rmw<1, 4><<<2048, 256>>>(tab, nrec, nupdates, seed++, sink); }, 2, &ms[0]);
-  if (!rc) rc = ubench_time([&] { k_ubench_rmw<0, 4><<<2048, 256>>>(tab, nrec, nupdates, seed++, sink); }, 2, &ms[1]);
-  if (!rc) rc = ubench_time([&] { k_ubench_rmw<2, 4><<<2048, 256>>>(tab, nrec, nupdates, seed++, sink); }, 2, &ms[2]);
-  (void)hipFree(tab); (void)hipFree(sink);
+  int rc = ubench_time([&] { k_ubench_rmw<1, 4><<<2048, 256>>>(tab.p, nrec, nupdates, seed++, sink.p); }, 2, &ms[0]);
+  if (!rc) rc = ubench_time([&] { k_ubench_rmw<0, 4><<<2048, 256>>>(tab.p, nrec, nupdates, seed++, sink.p); }, 2, &ms[1]);
+  if (!rc) rc = ubench_time([&] { k_ubench_rmw<2, 4><<<2048, 256>>>(tab.p, nrec, nupdates, seed++, sink.p); }, 2, &ms[2]);
   if (rc) return fail(MCX_ERR_HIP, "random-access microbenchmark failed");
   if (rmw_per_s) *rmw_per_s = (double)nupdates / ms[0] * 1e3;
   if (load16_per_s) *load16_per_s = (double)nupdates / ms[1] * 1e3;
@@ -4533,80 +4537,56 @@ template <int W>
 static int sort_records_t(uint8_t *recs, uint64_t n, uint32_t rec_bytes, int device, bool check_only, int64_t *first_unsorted)
 {
   hipStream_t st = nullptr;
-  uint8_t *d_in = nullptr, *d_out = nullptr;
-  uint64_t *d_k0 = nullptr, *d_k1 = nullptr, *d_ks = nullptr, *d_ks2 = nullptr, *d_idx = nullptr, *d_idx2 = nullptr;
-  unsigned long long *d_bad = nullptr;
-  void *d_tmp = nullptr;
-  size_t tmp_bytes = 0;
-  auto cleanup = [&]() {
-    (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_k0); (void)hipFree(d_k1); (void)hipFree(d_ks); (void)hipFree(d_ks2);
-    (void)hipFree(d_idx); (void)hipFree(d_idx2); (void)hipFree(d_bad); (void)hipFree(d_tmp);
-    if (st) (void)hipStreamDestroy(st);
-  };
-#define SRT_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess) {                                                               \
-      cleanup();                                                                          \
-      return fail(_e == hipErrorOutOfMemory ? MCX_ERR_NOMEM : MCX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
-    }                                                                                     \
-  } while (0)
-  SRT_TRY(hipSetDevice(device));
-  SRT_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  ScopeExit drop_stream([&] { (void)hipStreamDestroy(st); });  // (declared first: the buffers go before their stream)
+  DevBuf<uint8_t> d_in, d_out, d_tmp;
+  DevBuf<uint64_t> d_k0, d_k1, d_ks, d_ks2, d_idx, d_idx2;
+  DevBuf<unsigned long long> d_bad;
   const uint64_t bytes = n * rec_bytes;
-  SRT_TRY(hipMalloc((void **)&d_in, bytes));
-  SRT_TRY(hipMalloc((void **)&d_k0, n * 8));
-  if (W == 2) SRT_TRY(hipMalloc((void **)&d_k1, n * 8));
-  SRT_TRY(hipMemcpyAsync(d_in, recs, bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(d_in.alloc(bytes));
+  HIP_TRY(d_k0.alloc(n));
+  if (W == 2) HIP_TRY(d_k1.alloc(n));
+  HIP_TRY(hipMemcpyAsync(d_in, recs, bytes, hipMemcpyHostToDevice, st));
   const unsigned gb = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL((k_record_keys<W>), dim3(gb), dim3(256), 0, st, d_in, n, rec_bytes, d_k0, d_k1);
-  SRT_TRY(hipGetLastError());
+  hipLaunchKernelGGL((k_record_keys<W>), dim3(gb), dim3(256), 0, st, d_in.p, n, rec_bytes, d_k0.p, d_k1.p);
+  HIP_TRY(hipGetLastError());
   if (check_only) {
     unsigned long long bad = ~0ULL;
-    SRT_TRY(hipMalloc((void **)&d_bad, 8));
-    SRT_TRY(hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, st));
-    if (W > 2) hipLaunchKernelGGL(k_check_sorted_records, dim3(gb), dim3(256), 0, st, (const uint8_t *)d_in, rec_bytes, (uint32_t)W, n, d_bad);
-    else hipLaunchKernelGGL((k_check_sorted<W>), dim3(gb), dim3(256), 0, st, d_k0, d_k1, n, d_bad);
-    SRT_TRY(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st));
-    SRT_TRY(hipStreamSynchronize(st));
+    HIP_TRY(d_bad.alloc(1));
+    HIP_TRY(hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, st));
+    if (W > 2) hipLaunchKernelGGL(k_check_sorted_records, dim3(gb), dim3(256), 0, st, (const uint8_t *)d_in, rec_bytes, (uint32_t)W, n, d_bad.p);
+    else hipLaunchKernelGGL((k_check_sorted<W>), dim3(gb), dim3(256), 0, st, d_k0.p, d_k1.p, n, d_bad.p);
+    HIP_TRY(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     *first_unsorted = bad == ~0ULL ? -1 : (int64_t)bad;
-    cleanup();
     return MCX_OK;
   }
-  SRT_TRY(hipMalloc((void **)&d_idx, n * 8));
-  SRT_TRY(hipMalloc((void **)&d_idx2, n * 8));
-  SRT_TRY(hipMalloc((void **)&d_ks, n * 8));
-  hipLaunchKernelGGL(k_iota, dim3(gb), dim3(256), 0, st, d_idx, n);
-  const uint64_t *first_key = W == 2 ? d_k1 : d_k0;
-  SRT_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, first_key, d_ks, d_idx, d_idx2, n, 0, 64, st));
-  SRT_TRY(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
-  SRT_TRY(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, first_key, d_ks, d_idx, d_idx2, n, 0, 64, st));
-  uint64_t *perm = d_idx2;
-  if (W == 2) {  // LSD: stable second pass on the most significant word
-    SRT_TRY(hipMalloc((void **)&d_ks2, n * 8));
-    hipLaunchKernelGGL(k_gather_u64, dim3(gb), dim3(256), 0, st, (const uint64_t *)d_k0, (const uint64_t *)d_idx2, d_ks2, n);
-    SRT_TRY(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_ks2, d_ks, d_idx2, d_idx, n, 0, 64, st));
-    perm = d_idx;
-  }
-  if (W > 2) {  // k > 63: LSD over all W words, least significant first, each word fetched through the permutation so far
-    SRT_TRY(hipMalloc((void **)&d_ks2, n * 8));
-    hipLaunchKernelGGL(k_iota, dim3(gb), dim3(256), 0, st, d_idx, n);
-    uint64_t *cur = d_idx, *nxt = d_idx2;
-    for (int w = W - 1; w >= 0; w--) {
-      hipLaunchKernelGGL(k_gather_record_word, dim3(gb), dim3(256), 0, st, (const uint8_t *)d_in, rec_bytes, (const uint64_t *)cur, (uint32_t)w, d_ks2, n);
-      SRT_TRY(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_ks2, d_ks, cur, nxt, n, 0, 64, st));
-      std::swap(cur, nxt);
-    }
-    perm = cur;
-  }
-  (void)hipFree(d_ks); d_ks = nullptr;
-  SRT_TRY(hipMalloc((void **)&d_out, bytes));
-  hipLaunchKernelGGL(k_gather_records, dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), 0, st, d_in, (const uint64_t *)perm, n, rec_bytes, d_out);
-  SRT_TRY(hipGetLastError());
-  SRT_TRY(hipMemcpyAsync(recs, d_out, bytes, hipMemcpyDeviceToHost, st));
-  SRT_TRY(hipStreamSynchronize(st));
-#undef SRT_TRY
-  cleanup();
+  HIP_TRY(d_idx.alloc(n));
+  HIP_TRY(d_idx2.alloc(n));
+  HIP_TRY(d_ks.alloc(n));
+  hipLaunchKernelGGL(k_iota, dim3(gb), dim3(256), 0, st, d_idx.p, n);
+  size_t tmp_bytes = 0;
+  int rc = sort_perm_scratch(st, n, &tmp_bytes);
+  if (rc != MCX_OK) return rc;
+  HIP_TRY(d_tmp.alloc(tmp_bytes ? tmp_bytes : 16));
+  if (W >= 2) HIP_TRY(d_ks2.alloc(n));
+  // k_record_keys left the words of one- and two-word keys in d_k0 / d_k1; longer keys (k > 63) are fetched from the
+  // byte-packed records, a word per pass
+  auto word = [&](int w, bool first, const uint64_t *through, uint64_t *dst, const uint64_t **have) -> int {
+    if (W <= 2 && first) *have = W == 2 ? d_k1.p : d_k0.p;
+    else if (W == 2) hipLaunchKernelGGL(k_gather_u64, dim3(gb), dim3(256), 0, st, (const uint64_t *)d_k0, through, dst, n);
+    else hipLaunchKernelGGL(k_gather_record_word, dim3(gb), dim3(256), 0, st, (const uint8_t *)d_in, rec_bytes, through, (uint32_t)w, dst, n);
+    return MCX_OK;
+  };
+  uint64_t *const keys[2] = {d_ks.p, d_ks2.p}, *const perms[2] = {d_idx.p, d_idx2.p}, *perm = nullptr;
+  if ((rc = sort_perm_by_words(st, n, W, 64, keys, perms, d_tmp.p, tmp_bytes, nullptr, word, &perm)) != MCX_OK) return rc;
+  d_ks.release();  // (before d_out comes: this bounds the peak)
+  HIP_TRY(d_out.alloc(bytes));
+  hipLaunchKernelGGL(k_gather_records, dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), 0, st, d_in.p, (const uint64_t *)perm, n, rec_bytes, d_out.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(recs, d_out, bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return MCX_OK;
 }
 

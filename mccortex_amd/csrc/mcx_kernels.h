@@ -1531,12 +1531,7 @@ __global__ void k_iota(uint64_t *dst, uint64_t n)
 }
 
 // Keys of more than two words (k > 63): the LSD passes of a sort fetch one key word at a time, through the permutation
-// so far, from the table (export) or from byte-packed records (`sort`).
-__global__ void k_gather_keyword(TableView t, const uint64_t *slot_of, const uint64_t *perm, uint32_t w, uint64_t *dst, uint64_t n)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { const uint64_t x = key_ptr(t, slot_of[perm[i]])[w]; dst[i] = w ? x : (x & kKeyMask); }
-}
+// so far, from the table (export and unitigs: k_un_keyword, mcx_unitigs.h) or from byte-packed records (`sort`).
 __global__ void k_gather_record_word(const uint8_t *recs, uint32_t rec_bytes, const uint64_t *perm, uint32_t w, uint64_t *dst, uint64_t n)
 {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

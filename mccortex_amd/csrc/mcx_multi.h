@@ -83,14 +83,6 @@ struct mcx_group {
   bool peer_ok = true;  // every pair of distinct devices can map each other's memory (kernels may write to a peer)
 };
 
-#define GRP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess)                                                                          \
-      return fail(_e == hipErrorOutOfMemory ? MCX_ERR_NOMEM : MCX_ERR_HIP, "%s: %s (%s:%d)", #expr, \
-                  hipGetErrorString(_e), __FILE__, __LINE__);                                      \
-  } while (0)
-
 static void group_free_buffers(mcx_group *G)
 {
   for (int i = 0; i < G->n; i++) {
@@ -178,21 +170,21 @@ static int group_alloc_buffers(mcx_group *G)
     const uint64_t recb = 16ull * W;
     const uint64_t blk_recs = (uint64_t)G->sk_segs * G->sk_cap;
     for (int i = 0; i < N; i++) {
-      GRP_TRY(hipSetDevice(G->part[i]->device));
+      HIP_TRY(hipSetDevice(G->part[i]->device));
       for (int b = 0; b < kSets; b++) {
         XBuf &s = G->send[i][b];
-        GRP_TRY(hipMalloc((void **)&s.recs, (uint64_t)N * blk_recs * recb));
-        GRP_TRY(hipMalloc((void **)&s.fills_rm, (uint64_t)N * G->sk_segs * 8));
-        GRP_TRY(hipMalloc((void **)&s.fills, (uint64_t)N * G->sk_segs * 8));
-        GRP_TRY(hipMalloc((void **)&s.sp_recs, G->sp_cap * recb));
-        GRP_TRY(hipMalloc((void **)&s.sp_own, G->sp_cap));
-        GRP_TRY(hipMalloc((void **)&s.sp_count, 8));
-        GRP_TRY(hipHostMalloc((void **)&G->h_spill[i][b], 8, hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void **)&s.recs, (uint64_t)N * blk_recs * recb));
+        HIP_TRY(hipMalloc((void **)&s.fills_rm, (uint64_t)N * G->sk_segs * 8));
+        HIP_TRY(hipMalloc((void **)&s.fills, (uint64_t)N * G->sk_segs * 8));
+        HIP_TRY(hipMalloc((void **)&s.sp_recs, G->sp_cap * recb));
+        HIP_TRY(hipMalloc((void **)&s.sp_own, G->sp_cap));
+        HIP_TRY(hipMalloc((void **)&s.sp_count, 8));
+        HIP_TRY(hipHostMalloc((void **)&G->h_spill[i][b], 8, hipHostMallocDefault));
         *G->h_spill[i][b] = 0;
         for (int src = 0; src < N; src++) {
           XBuf &r = G->recv[i][src][b];
-          GRP_TRY(hipMalloc((void **)&r.recs, blk_recs * recb));
-          GRP_TRY(hipMalloc((void **)&r.fills, (uint64_t)G->sk_segs * 8));
+          HIP_TRY(hipMalloc((void **)&r.recs, blk_recs * recb));
+          HIP_TRY(hipMalloc((void **)&r.fills, (uint64_t)G->sk_segs * 8));
         }
       }
     }
@@ -200,24 +192,24 @@ static int group_alloc_buffers(mcx_group *G)
   }
   const uint64_t blk = (uint64_t)G->segs * G->seg_cap;  // tuples of one owner's block
   for (int i = 0; i < N; i++) {
-    GRP_TRY(hipSetDevice(G->part[i]->device));
+    HIP_TRY(hipSetDevice(G->part[i]->device));
     for (int b = 0; b < kSets; b++) {
       XBuf &s = G->send[i][b];
-      GRP_TRY(hipMalloc((void **)&s.keys, (uint64_t)N * blk * 8 * W));
-      GRP_TRY(hipMalloc((void **)&s.counts, (uint64_t)N * G->segs * 8));
-      GRP_TRY(hipMalloc((void **)&s.ov_keys, ((uint64_t)N * G->ov_cap + G->sp_cap) * 8 * W));
-      GRP_TRY(hipMalloc((void **)&s.ov_edges, (uint64_t)N * G->ov_cap + G->sp_cap));
-      GRP_TRY(hipMalloc((void **)&s.ov_counts, (uint64_t)(N + 2) * 8));
-      GRP_TRY(hipMemcpy(s.ov_counts + N + 1, &G->sp_cap, 8, hipMemcpyHostToDevice));
-      GRP_TRY(hipHostMalloc((void **)&G->h_spill[i][b], 8, hipHostMallocDefault));
+      HIP_TRY(hipMalloc((void **)&s.keys, (uint64_t)N * blk * 8 * W));
+      HIP_TRY(hipMalloc((void **)&s.counts, (uint64_t)N * G->segs * 8));
+      HIP_TRY(hipMalloc((void **)&s.ov_keys, ((uint64_t)N * G->ov_cap + G->sp_cap) * 8 * W));
+      HIP_TRY(hipMalloc((void **)&s.ov_edges, (uint64_t)N * G->ov_cap + G->sp_cap));
+      HIP_TRY(hipMalloc((void **)&s.ov_counts, (uint64_t)(N + 2) * 8));
+      HIP_TRY(hipMemcpy(s.ov_counts + N + 1, &G->sp_cap, 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipHostMalloc((void **)&G->h_spill[i][b], 8, hipHostMallocDefault));
       *G->h_spill[i][b] = 0;
       for (int src = 0; src < N; src++) {
         XBuf &r = G->recv[i][src][b];
-        GRP_TRY(hipMalloc((void **)&r.keys, blk * 8 * W));
-        GRP_TRY(hipMalloc((void **)&r.counts, (uint64_t)G->segs * 8));
-        GRP_TRY(hipMalloc((void **)&r.ov_keys, G->ov_cap * 8 * W));
-        GRP_TRY(hipMalloc((void **)&r.ov_edges, G->ov_cap));
-        GRP_TRY(hipMalloc((void **)&r.ov_counts, 8));
+        HIP_TRY(hipMalloc((void **)&r.keys, blk * 8 * W));
+        HIP_TRY(hipMalloc((void **)&r.counts, (uint64_t)G->segs * 8));
+        HIP_TRY(hipMalloc((void **)&r.ov_keys, G->ov_cap * 8 * W));
+        HIP_TRY(hipMalloc((void **)&r.ov_edges, G->ov_cap));
+        HIP_TRY(hipMalloc((void **)&r.ov_counts, 8));
       }
     }
   }
@@ -273,8 +265,8 @@ static int group_route_spill(mcx_group *G, int idx, int b)
 {
   if (!G->used[idx][b]) return MCX_OK;
   mcx_graph *me = G->part[idx];
-  GRP_TRY(hipSetDevice(me->device));
-  GRP_TRY(hipEventSynchronize(G->filled[idx][b]));
+  HIP_TRY(hipSetDevice(me->device));
+  HIP_TRY(hipEventSynchronize(G->filled[idx][b]));
   const uint64_t n = std::min<uint64_t>(*G->h_spill[idx][b], G->sp_cap);
   if (!n) return MCX_OK;
   *G->h_spill[idx][b] = 0;
@@ -285,45 +277,45 @@ static int group_route_spill(mcx_group *G, int idx, int b)
     const uint64_t recb = 16ull * W;
     for (int j = 0; j < N; j++) {
       mcx_graph *own = G->part[j];
-      GRP_TRY(hipSetDevice(own->device));
+      HIP_TRY(hipSetDevice(own->device));
       DevBuf<uint8_t> r, o, d;  // (freed on every way out; the owner's stream is synchronised before the normal one)
       DevBuf<unsigned long long> cnt;
-      GRP_TRY(r.alloc(n * recb));
-      GRP_TRY(o.alloc(n));
-      GRP_TRY(d.alloc(n * recb));
-      GRP_TRY(cnt.alloc(1));
-      GRP_TRY(hipMemcpyPeerAsync(r, own->device, s.sp_recs, me->device, n * recb, own->stream));
-      GRP_TRY(hipMemcpyPeerAsync(o, own->device, s.sp_own, me->device, n, own->stream));
-      GRP_TRY(hipMemsetAsync(cnt, 0, 8, own->stream));
+      HIP_TRY(r.alloc(n * recb));
+      HIP_TRY(o.alloc(n));
+      HIP_TRY(d.alloc(n * recb));
+      HIP_TRY(cnt.alloc(1));
+      HIP_TRY(hipMemcpyPeerAsync(r, own->device, s.sp_recs, me->device, n * recb, own->stream));
+      HIP_TRY(hipMemcpyPeerAsync(o, own->device, s.sp_own, me->device, n, own->stream));
+      HIP_TRY(hipMemsetAsync(cnt, 0, 8, own->stream));
       const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255) / 256, 4096);
       if (W == 1) hipLaunchKernelGGL(k_superk_pick<1>, dim3(blocks), dim3(256), 0, own->stream, (const void *)r.p, (const uint8_t *)o.p, n, (uint32_t)j, (void *)d.p, cnt.p);
       else hipLaunchKernelGGL(k_superk_pick<2>, dim3(blocks), dim3(256), 0, own->stream, (const void *)r.p, (const uint8_t *)o.p, n, (uint32_t)j, (void *)d.p, cnt.p);
-      GRP_TRY(hipGetLastError());
+      HIP_TRY(hipGetLastError());
       int rc = mcx_graph_add_superk_dev(own, colour, d.p, cnt.p, 1, n, n * 16);
       const hipError_t se = hipStreamSynchronize(own->stream);  // the buffers are released when this scope ends
       if (rc != MCX_OK) return rc;
-      GRP_TRY(se);  // (an asynchronous fault of the pick / the owner kernel is reported here, at the piece that caused it)
+      HIP_TRY(se);  // (an asynchronous fault of the pick / the owner kernel is reported here, at the piece that caused it)
     }
-    GRP_TRY(hipSetDevice(me->device));
+    HIP_TRY(hipSetDevice(me->device));
     return MCX_OK;
   }
   const uint64_t at = (uint64_t)N * G->ov_cap;
   for (int j = 0; j < N; j++) {
     mcx_graph *own = G->part[j];
-    GRP_TRY(hipSetDevice(own->device));
+    HIP_TRY(hipSetDevice(own->device));
     DevBuf<uint64_t> k;
     DevBuf<uint8_t> e;
-    GRP_TRY(k.alloc(n * W));
-    GRP_TRY(e.alloc(n));
-    GRP_TRY(hipMemcpyPeerAsync(k.p, own->device, s.ov_keys + at * W, me->device, n * 8 * W, own->stream));
-    GRP_TRY(hipMemcpyPeerAsync(e.p, own->device, s.ov_edges + at, me->device, n, own->stream));
+    HIP_TRY(k.alloc(n * W));
+    HIP_TRY(e.alloc(n));
+    HIP_TRY(hipMemcpyPeerAsync(k.p, own->device, s.ov_keys + at * W, me->device, n * 8 * W, own->stream));
+    HIP_TRY(hipMemcpyPeerAsync(e.p, own->device, s.ov_edges + at, me->device, n, own->stream));
     DISPATCH_WC(own, launch_insert_tuples_t, own, colour, (const uint64_t *)k.p, (const uint8_t *)e.p, n, 1u);
     const hipError_t le = hipGetLastError();
     const hipError_t se = hipStreamSynchronize(own->stream);  // the buffers are released when this scope ends
-    GRP_TRY(le);
-    GRP_TRY(se);
+    HIP_TRY(le);
+    HIP_TRY(se);
   }
-  GRP_TRY(hipSetDevice(me->device));
+  HIP_TRY(hipSetDevice(me->device));
   return MCX_OK;
 }
 
@@ -348,10 +340,10 @@ static int group_submit_stream(mcx_group *G, int idx, const StreamLaunch &L, int
       rc = group_route_spill(G, idx, b);  // what this set's previous piece spilled (nearly always nothing)
       if (rc != MCX_OK) return rc;
       // 1. sender: minimizers, per-owner records
-      GRP_TRY(hipSetDevice(me->device));
-      if (G->used[idx][b]) GRP_TRY(hipStreamWaitEvent(me->stream, G->sent[idx][b], 0));  // its last copies have left
-      GRP_TRY(hipMemsetAsync(s.fills_rm, 0, (uint64_t)N * G->sk_segs * 8, me->stream));
-      GRP_TRY(hipMemsetAsync(s.sp_count, 0, 8, me->stream));
+      HIP_TRY(hipSetDevice(me->device));
+      if (G->used[idx][b]) HIP_TRY(hipStreamWaitEvent(me->stream, G->sent[idx][b], 0));  // its last copies have left
+      HIP_TRY(hipMemsetAsync(s.fills_rm, 0, (uint64_t)N * G->sk_segs * 8, me->stream));
+      HIP_TRY(hipMemsetAsync(s.sp_count, 0, 8, me->stream));
       StreamLaunch P = L;
       P.pos_lo = lo; P.pos_hi = hi;
       SuperkOut so{s.recs, s.fills_rm, G->sk_cap, lbo, G->sk_segs, s.sp_recs, s.sp_own, s.sp_count, G->sp_cap};
@@ -359,33 +351,33 @@ static int group_submit_stream(mcx_group *G, int idx, const StreamLaunch &L, int
       if (rc != MCX_OK) return rc;
       hipLaunchKernelGGL(k_transpose_fills, dim3(((unsigned)N * G->sk_segs + 63) / 64), dim3(64), 0, me->stream,
                          (const unsigned long long *)s.fills_rm, s.fills, G->sk_segs, (uint32_t)N);
-      GRP_TRY(hipGetLastError());
-      GRP_TRY(hipMemcpyAsync(G->h_spill[idx][b], s.sp_count, 8, hipMemcpyDeviceToHost, me->stream));
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(G->h_spill[idx][b], s.sp_count, 8, hipMemcpyDeviceToHost, me->stream));
       G->spill_colour[idx][b] = colour;
-      GRP_TRY(hipEventRecord(G->filled[idx][b], me->stream));
+      HIP_TRY(hipEventRecord(G->filled[idx][b], me->stream));
       // 2. one copy of the fills and one of the records per owner: whole segments, so no count is read on the host
-      GRP_TRY(hipStreamWaitEvent(G->cs[idx], G->filled[idx][b], 0));
+      HIP_TRY(hipStreamWaitEvent(G->cs[idx], G->filled[idx][b], 0));
       if (group_copy_kernel(G)) {  // the filled parts only, one launch (k_copy_filled)
         PeerDst pd{};
         for (int j = 0; j < N; j++) {
-          if (G->used[idx][b]) GRP_TRY(hipStreamWaitEvent(G->cs[idx], G->consumed[j][idx][b], 0));  // the slot is free again
+          if (G->used[idx][b]) HIP_TRY(hipStreamWaitEvent(G->cs[idx], G->consumed[j][idx][b], 0));  // the slot is free again
           pd.data[j] = G->recv[j][idx][b].recs;
           pd.fills[j] = G->recv[j][idx][b].fills;
         }
         hipLaunchKernelGGL(k_copy_filled, dim3(2048), dim3(256), 0, G->cs[idx], (const ulonglong2 *)s.recs, (const unsigned long long *)s.fills, pd,
                            (uint32_t)N, G->sk_segs, G->sk_cap, (uint32_t)recb);
-        GRP_TRY(hipGetLastError());
-        for (int j = 0; j < N; j++) GRP_TRY(hipEventRecord(G->arrived[j][idx][b], G->cs[idx]));
+        HIP_TRY(hipGetLastError());
+        for (int j = 0; j < N; j++) HIP_TRY(hipEventRecord(G->arrived[j][idx][b], G->cs[idx]));
       } else
       for (int j = 0; j < N; j++) {
         mcx_graph *own = G->part[j];
         XBuf &r = G->recv[j][idx][b];
-        if (G->used[idx][b]) GRP_TRY(hipStreamWaitEvent(G->cs[idx], G->consumed[j][idx][b], 0));  // the slot is free again
-        GRP_TRY(hipMemcpyPeerAsync(r.fills, own->device, s.fills + (uint64_t)j * G->sk_segs, me->device, (uint64_t)G->sk_segs * 8, G->cs[idx]));
-        GRP_TRY(hipMemcpyPeerAsync(r.recs, own->device, (const uint8_t *)s.recs + (uint64_t)j * blk_recs * recb, me->device, blk_recs * recb, G->cs[idx]));
-        GRP_TRY(hipEventRecord(G->arrived[j][idx][b], G->cs[idx]));
+        if (G->used[idx][b]) HIP_TRY(hipStreamWaitEvent(G->cs[idx], G->consumed[j][idx][b], 0));  // the slot is free again
+        HIP_TRY(hipMemcpyPeerAsync(r.fills, own->device, s.fills + (uint64_t)j * G->sk_segs, me->device, (uint64_t)G->sk_segs * 8, G->cs[idx]));
+        HIP_TRY(hipMemcpyPeerAsync(r.recs, own->device, (const uint8_t *)s.recs + (uint64_t)j * blk_recs * recb, me->device, blk_recs * recb, G->cs[idx]));
+        HIP_TRY(hipEventRecord(G->arrived[j][idx][b], G->cs[idx]));
       }
-      GRP_TRY(hipEventRecord(G->sent[idx][b], G->cs[idx]));
+      HIP_TRY(hipEventRecord(G->sent[idx][b], G->cs[idx]));
       // 3. owners: k-merise what arrived into their region bins.  The reservation is a true upper bound -- every start
       // position of the piece may belong to one owner -- and what the records really held comes off the owner's books
       // when the launch has settled (Counters::binned, snap_*).  (Until round 5 it was an estimate, 1.25 x piece / N:
@@ -394,16 +386,16 @@ static int group_submit_stream(mcx_group *G, int idx, const StreamLaunch &L, int
       for (int j = 0; j < N; j++) {
         mcx_graph *own = G->part[j];
         XBuf &r = G->recv[j][idx][b];
-        GRP_TRY(hipSetDevice(own->device));
-        GRP_TRY(hipStreamWaitEvent(own->stream, G->arrived[j][idx][b], 0));
+        HIP_TRY(hipSetDevice(own->device));
+        HIP_TRY(hipStreamWaitEvent(own->stream, G->arrived[j][idx][b], 0));
         rc = mcx_graph_add_superk_dev(own, colour, r.recs, r.fills, G->sk_segs, G->sk_cap, std::min(share, blk_recs * 16));
         if (rc != MCX_OK) return rc;
-        GRP_TRY(hipEventRecord(G->consumed[j][idx][b], own->stream));
+        HIP_TRY(hipEventRecord(G->consumed[j][idx][b], own->stream));
       }
       G->used[idx][b] = true;
       lo = hi;
     }
-    GRP_TRY(hipSetDevice(me->device));
+    HIP_TRY(hipSetDevice(me->device));
     return MCX_OK;
   }
   const uint64_t blk = (uint64_t)G->segs * G->seg_cap;
@@ -415,25 +407,25 @@ static int group_submit_stream(mcx_group *G, int idx, const StreamLaunch &L, int
     rc = group_route_spill(G, idx, b);  // what this set's previous piece spilled (nearly always nothing)
     if (rc != MCX_OK) return rc;
     // 1. sender
-    GRP_TRY(hipSetDevice(me->device));
-    if (G->used[idx][b]) GRP_TRY(hipStreamWaitEvent(me->stream, G->sent[idx][b], 0));  // its last copies have left
-    GRP_TRY(hipMemsetAsync(s.counts, 0, (uint64_t)N * G->segs * 8, me->stream));
-    GRP_TRY(hipMemsetAsync(s.ov_counts, 0, (uint64_t)(N + 1) * 8, me->stream));
+    HIP_TRY(hipSetDevice(me->device));
+    if (G->used[idx][b]) HIP_TRY(hipStreamWaitEvent(me->stream, G->sent[idx][b], 0));  // its last copies have left
+    HIP_TRY(hipMemsetAsync(s.counts, 0, (uint64_t)N * G->segs * 8, me->stream));
+    HIP_TRY(hipMemsetAsync(s.ov_counts, 0, (uint64_t)(N + 1) * 8, me->stream));
     StreamLaunch P = L;
     P.pos_lo = lo; P.pos_hi = hi;
     rc = shard_bins_launch(me, P, s.keys, s.counts, G->seg_cap, s.ov_keys, s.ov_edges, s.ov_counts, G->ov_cap, true);
     if (rc != MCX_OK) return rc;
-    GRP_TRY(hipMemcpyAsync(G->h_spill[idx][b], s.ov_counts + N, 8, hipMemcpyDeviceToHost, me->stream));
+    HIP_TRY(hipMemcpyAsync(G->h_spill[idx][b], s.ov_counts + N, 8, hipMemcpyDeviceToHost, me->stream));
     G->spill_colour[idx][b] = colour;
-    GRP_TRY(hipEventRecord(G->filled[idx][b], me->stream));
+    HIP_TRY(hipEventRecord(G->filled[idx][b], me->stream));
     // 2. one copy per (owner, buffer): fixed sizes, so the fills travel with the blocks and the host
     // never has to read them
-    GRP_TRY(hipStreamWaitEvent(G->cs[idx], G->filled[idx][b], 0));
+    HIP_TRY(hipStreamWaitEvent(G->cs[idx], G->filled[idx][b], 0));
     const bool ck = group_copy_kernel(G);
     if (ck) {  // the packed tuples: filled parts of all (owner, segment) bins in one launch; the overflow bins below as before
       PeerDst pd{};
       for (int j = 0; j < N; j++) {
-        if (G->used[idx][b]) GRP_TRY(hipStreamWaitEvent(G->cs[idx], G->consumed[j][idx][b], 0));  // the slot is free again
+        if (G->used[idx][b]) HIP_TRY(hipStreamWaitEvent(G->cs[idx], G->consumed[j][idx][b], 0));  // the slot is free again
         pd.data[j] = G->recv[j][idx][b].keys;
         pd.fills[j] = G->recv[j][idx][b].counts;
       }
@@ -446,40 +438,40 @@ static int group_submit_stream(mcx_group *G, int idx, const StreamLaunch &L, int
       for (int j = 0; j < N; j++) pd.data[j] = G->recv[j][idx][b].ov_edges;
       hipLaunchKernelGGL(k_copy_filled, dim3(256), dim3(256), 0, G->cs[idx], (const ulonglong2 *)s.ov_edges, (const unsigned long long *)s.ov_counts, pd,
                          (uint32_t)N, 1u, G->ov_cap, 1u);
-      GRP_TRY(hipGetLastError());
+      HIP_TRY(hipGetLastError());
     }
     for (int j = 0; j < N; j++) {
       mcx_graph *own = G->part[j];
       XBuf &r = G->recv[j][idx][b];
       if (!ck) {
-        if (G->used[idx][b]) GRP_TRY(hipStreamWaitEvent(G->cs[idx], G->consumed[j][idx][b], 0));  // the slot is free again
-        GRP_TRY(hipMemcpyPeerAsync(r.counts, own->device, s.counts + (uint64_t)j * G->segs, me->device, (uint64_t)G->segs * 8, G->cs[idx]));
-        GRP_TRY(hipMemcpyPeerAsync(r.keys, own->device, s.keys + (uint64_t)j * blk * W, me->device, blk * 8 * W, G->cs[idx]));
-        GRP_TRY(hipMemcpyPeerAsync(r.ov_counts, own->device, s.ov_counts + j, me->device, 8, G->cs[idx]));
-        GRP_TRY(hipMemcpyPeerAsync(r.ov_keys, own->device, s.ov_keys + (uint64_t)j * G->ov_cap * W, me->device, G->ov_cap * 8 * W, G->cs[idx]));
-        GRP_TRY(hipMemcpyPeerAsync(r.ov_edges, own->device, s.ov_edges + (uint64_t)j * G->ov_cap, me->device, G->ov_cap, G->cs[idx]));
+        if (G->used[idx][b]) HIP_TRY(hipStreamWaitEvent(G->cs[idx], G->consumed[j][idx][b], 0));  // the slot is free again
+        HIP_TRY(hipMemcpyPeerAsync(r.counts, own->device, s.counts + (uint64_t)j * G->segs, me->device, (uint64_t)G->segs * 8, G->cs[idx]));
+        HIP_TRY(hipMemcpyPeerAsync(r.keys, own->device, s.keys + (uint64_t)j * blk * W, me->device, blk * 8 * W, G->cs[idx]));
+        HIP_TRY(hipMemcpyPeerAsync(r.ov_counts, own->device, s.ov_counts + j, me->device, 8, G->cs[idx]));
+        HIP_TRY(hipMemcpyPeerAsync(r.ov_keys, own->device, s.ov_keys + (uint64_t)j * G->ov_cap * W, me->device, G->ov_cap * 8 * W, G->cs[idx]));
+        HIP_TRY(hipMemcpyPeerAsync(r.ov_edges, own->device, s.ov_edges + (uint64_t)j * G->ov_cap, me->device, G->ov_cap, G->cs[idx]));
       }
-      GRP_TRY(hipEventRecord(G->arrived[j][idx][b], G->cs[idx]));
+      HIP_TRY(hipEventRecord(G->arrived[j][idx][b], G->cs[idx]));
     }
-    GRP_TRY(hipEventRecord(G->sent[idx][b], G->cs[idx]));
+    HIP_TRY(hipEventRecord(G->sent[idx][b], G->cs[idx]));
     // 3. owners: split by sub-table; the overflow bins take the full-tuple path.  Booked with a true upper bound:
     // an owner's block holds at most `blk` tuples, and a piece at most hi - lo.
     const uint64_t share = hi - lo;
     for (int j = 0; j < N; j++) {
       mcx_graph *own = G->part[j];
       XBuf &r = G->recv[j][idx][b];
-      GRP_TRY(hipSetDevice(own->device));
-      GRP_TRY(hipStreamWaitEvent(own->stream, G->arrived[j][idx][b], 0));
+      HIP_TRY(hipSetDevice(own->device));
+      HIP_TRY(hipStreamWaitEvent(own->stream, G->arrived[j][idx][b], 0));
       rc = mcx_graph_add_segments_dev(own, colour, r.keys, r.counts, G->segs, G->seg_cap, std::min(share, blk));
       if (rc != MCX_OK) return rc;
       rc = mcx_graph_insert_tuple_segments_dev(own, colour, r.ov_keys, r.ov_edges, r.ov_counts, 1, G->ov_cap);
       if (rc != MCX_OK) return rc;
-      GRP_TRY(hipEventRecord(G->consumed[j][idx][b], own->stream));
+      HIP_TRY(hipEventRecord(G->consumed[j][idx][b], own->stream));
     }
     G->used[idx][b] = true;
     lo = hi;
   }
-  GRP_TRY(hipSetDevice(me->device));
+  HIP_TRY(hipSetDevice(me->device));
   return MCX_OK;
 }
 
@@ -633,6 +625,7 @@ extern "C" int mcx_graph_create_multi(mcx_graph **out, int kmer_size, int ncols,
   const uint64_t min_shard = 64ull << sub_shift_for_words(W);
   const uint64_t per = std::max<uint64_t>((capacity_kmers + (uint64_t)ndevices - 1) / (uint64_t)ndevices, min_shard);
   mcx_group *G = new mcx_group();
+  ScopeExit half_built([&] { group_destroy(G); });  // dismissed when the facade takes it
   G->n = ndevices;
   G->part.assign(ndevices, nullptr);
   {
@@ -645,7 +638,7 @@ extern "C" int mcx_graph_create_multi(mcx_graph **out, int kmer_size, int ncols,
     // v3: an ordinary table per device (the keys are dealt out by minimizer); v2: a hash-prefix shard
     int rc = G->v3 ? mcx_graph_create(&G->part[i], kmer_size, ncols, per, devices[i])
                    : mcx_graph_create_shard(&G->part[i], kmer_size, ncols, per, devices[i], ndevices, i);
-    if (rc != MCX_OK) { group_destroy(G); return rc; }
+    if (rc != MCX_OK) return rc;
     G->part[i]->group = G;
     G->part[i]->gidx = i;
     if (G->v3) G->part[i]->own_lbo = lbo;
@@ -657,9 +650,8 @@ extern "C" int mcx_graph_create_multi(mcx_graph **out, int kmer_size, int ncols,
   G->consumed.assign(ndevices, std::vector<std::array<hipEvent_t, kSets>>(ndevices, std::array<hipEvent_t, kSets>{}));
   G->cur.assign(ndevices, 0);
   G->used.assign(ndevices, {});
-#define MK_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { int rc_ = fail(MCX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); group_destroy(G); return rc_; } } while (0)
   for (int i = 0; i < ndevices; i++) {
-    MK_TRY(hipSetDevice(devices[i]));
+    HIP_TRY(hipSetDevice(devices[i]));
     for (int j = 0; j < ndevices; j++)  // direct xGMI copies instead of staging through the host
       if (devices[j] != devices[i]) {
         int can = 0;
@@ -670,20 +662,20 @@ extern "C" int mcx_graph_create_multi(mcx_graph **out, int kmer_size, int ncols,
           G->peer_ok = false;
         }
       }
-    MK_TRY(hipStreamCreateWithFlags(&G->cs[i], hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&G->cs[i], hipStreamNonBlocking));
     for (int b = 0; b < kSets; b++) {
-      MK_TRY(hipEventCreateWithFlags(&G->filled[i][b], hipEventDisableTiming));
-      MK_TRY(hipEventCreateWithFlags(&G->sent[i][b], hipEventDisableTiming));
-      for (int j = 0; j < ndevices; j++) MK_TRY(hipEventCreateWithFlags(&G->arrived[j][i][b], hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&G->filled[i][b], hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&G->sent[i][b], hipEventDisableTiming));
+      for (int j = 0; j < ndevices; j++) HIP_TRY(hipEventCreateWithFlags(&G->arrived[j][i][b], hipEventDisableTiming));
     }
   }
   for (int j = 0; j < ndevices; j++) {
-    MK_TRY(hipSetDevice(devices[j]));
+    HIP_TRY(hipSetDevice(devices[j]));
     for (int i = 0; i < ndevices; i++)
-      for (int b = 0; b < kSets; b++) MK_TRY(hipEventCreateWithFlags(&G->consumed[j][i][b], hipEventDisableTiming));
+      for (int b = 0; b < kSets; b++) HIP_TRY(hipEventCreateWithFlags(&G->consumed[j][i][b], hipEventDisableTiming));
   }
-#undef MK_TRY
   group_peer_selftest(G, devices);
+  half_built.dismiss();
   mcx_graph *f = new mcx_graph();  // the facade: no device state of its own
   f->k = kmer_size; f->W = W; f->ncols = ncols; f->ncols_vis = ncols;
   f->device = devices[0];
@@ -705,9 +697,9 @@ static int grp_drain(mcx_group *G)
         if (rc != MCX_OK) return rc;
       }
   for (int i = 0; i < G->n; i++) {
-    GRP_TRY(hipSetDevice(G->part[i]->device));
-    GRP_TRY(hipStreamSynchronize(G->part[i]->stream));
-    GRP_TRY(hipStreamSynchronize(G->cs[i]));
+    HIP_TRY(hipSetDevice(G->part[i]->device));
+    HIP_TRY(hipStreamSynchronize(G->part[i]->stream));
+    HIP_TRY(hipStreamSynchronize(G->cs[i]));
   }
   return MCX_OK;
 }
@@ -778,7 +770,7 @@ static int grp_add_reads_must_exist(mcx_group *G, int colour, const uint8_t *bas
   std::vector<uint8_t *> d_bases(N, nullptr), d_quals(N, nullptr), d_present(N, nullptr);
   std::vector<uint64_t *> d_off(N, nullptr);
   uint8_t *d_tmp = nullptr;  // on device 0
-  auto cleanup = [&]() {
+  ScopeExit release([&] {  // (a shard's stream has finished with its buffers before they go)
     for (int i = 0; i < N; i++) {
       (void)hipSetDevice(G->part[i]->device);
       (void)hipStreamSynchronize(G->part[i]->stream);
@@ -786,8 +778,7 @@ static int grp_add_reads_must_exist(mcx_group *G, int colour, const uint8_t *bas
     }
     (void)hipSetDevice(G->part[0]->device);
     (void)hipFree(d_tmp);
-  };
-#define ISEC_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { int rc_ = fail(_e == hipErrorOutOfMemory ? MCX_ERR_NOMEM : MCX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); cleanup(); return rc_; } } while (0)
+  });
   const unsigned blocks = (unsigned)((nreads + 127) / 128);
   auto launch = [&](int i, uint32_t phase) {
     mcx_graph *g = G->part[i];
@@ -800,38 +791,36 @@ static int grp_add_reads_must_exist(mcx_group *G, int colour, const uint8_t *bas
   };
   for (int i = 0; i < N; i++) {  // upload, phase 1
     mcx_graph *g = G->part[i];
-    ISEC_TRY(hipSetDevice(g->device));
-    ISEC_TRY(hipMalloc((void **)&d_bases[i], nb + 16));
-    ISEC_TRY(hipMalloc((void **)&d_off[i], (nreads + 1) * 8));
-    ISEC_TRY(hipMalloc((void **)&d_present[i], nb + 16));
-    if (quals && fq > 0) ISEC_TRY(hipMalloc((void **)&d_quals[i], nb + 16));
-    ISEC_TRY(hipMemcpyAsync(d_bases[i], bases + base0, nb, hipMemcpyHostToDevice, g->stream));
-    if (d_quals[i]) ISEC_TRY(hipMemcpyAsync(d_quals[i], quals + base0, nb, hipMemcpyHostToDevice, g->stream));
-    ISEC_TRY(hipMemcpyAsync(d_off[i], rel.data(), (nreads + 1) * 8, hipMemcpyHostToDevice, g->stream));
-    ISEC_TRY(hipMemsetAsync(d_present[i], 0, nb + 16, g->stream));
+    HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipMalloc((void **)&d_bases[i], nb + 16));
+    HIP_TRY(hipMalloc((void **)&d_off[i], (nreads + 1) * 8));
+    HIP_TRY(hipMalloc((void **)&d_present[i], nb + 16));
+    if (quals && fq > 0) HIP_TRY(hipMalloc((void **)&d_quals[i], nb + 16));
+    HIP_TRY(hipMemcpyAsync(d_bases[i], bases + base0, nb, hipMemcpyHostToDevice, g->stream));
+    if (d_quals[i]) HIP_TRY(hipMemcpyAsync(d_quals[i], quals + base0, nb, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(d_off[i], rel.data(), (nreads + 1) * 8, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemsetAsync(d_present[i], 0, nb + 16, g->stream));
     launch(i, 1u);
-    ISEC_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
-  for (int i = 0; i < N; i++) { ISEC_TRY(hipSetDevice(G->part[i]->device)); ISEC_TRY(hipStreamSynchronize(G->part[i]->stream)); }
+  for (int i = 0; i < N; i++) { HIP_TRY(hipSetDevice(G->part[i]->device)); HIP_TRY(hipStreamSynchronize(G->part[i]->stream)); }
   {  // OR the shards' answers on device 0, hand the result back
     mcx_graph *g0 = G->part[0];
-    ISEC_TRY(hipSetDevice(g0->device));
-    ISEC_TRY(hipMalloc((void **)&d_tmp, nb + 16));
+    HIP_TRY(hipSetDevice(g0->device));
+    HIP_TRY(hipMalloc((void **)&d_tmp, nb + 16));
     for (int i = 1; i < N; i++) {
-      ISEC_TRY(hipMemcpyPeerAsync(d_tmp, g0->device, d_present[i], G->part[i]->device, nb, g0->stream));
+      HIP_TRY(hipMemcpyPeerAsync(d_tmp, g0->device, d_present[i], G->part[i]->device, nb, g0->stream));
       hipLaunchKernelGGL(k_or_bytes, dim3((unsigned)std::min<uint64_t>((nb + 255) / 256, 4096)), dim3(256), 0, g0->stream, d_present[0], (const uint8_t *)d_tmp, nb);
-      ISEC_TRY(hipGetLastError());
+      HIP_TRY(hipGetLastError());
     }
-    ISEC_TRY(hipStreamSynchronize(g0->stream));
-    for (int i = 1; i < N; i++) ISEC_TRY(hipMemcpyPeer(d_present[i], G->part[i]->device, d_present[0], g0->device, nb));
+    HIP_TRY(hipStreamSynchronize(g0->stream));
+    for (int i = 1; i < N; i++) HIP_TRY(hipMemcpyPeer(d_present[i], G->part[i]->device, d_present[0], g0->device, nb));
   }
   for (int i = 0; i < N; i++) {  // phase 2
-    ISEC_TRY(hipSetDevice(G->part[i]->device));
+    HIP_TRY(hipSetDevice(G->part[i]->device));
     launch(i, 2u);
-    ISEC_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
-  cleanup();
-#undef ISEC_TRY
   return MCX_OK;
 }
 
@@ -867,15 +856,14 @@ static int grp_add_reads_pcr(mcx_group *G, int colour, const uint8_t *bases, con
   std::vector<std::unique_ptr<CutJob>> J;
   std::vector<uint8_t *> claims(N, nullptr);     // on shard j: claims of all shards, [N][nreads]
   std::vector<hipEvent_t> claimed(N, nullptr);   // shard i's own claims are ready
-  auto cleanup = [&]() {
+  ScopeExit release([&] {  // (runs before J's uploads go)
     for (int i = 0; i < N; i++) {
       (void)hipSetDevice(G->part[i]->device);
       (void)hipStreamSynchronize(G->part[i]->stream);
       (void)hipFree(claims[i]);
       if (claimed[i]) (void)hipEventDestroy(claimed[i]);
     }
-  };
-#define PCR_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { int rc_ = fail(_e == hipErrorOutOfMemory ? MCX_ERR_NOMEM : MCX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); cleanup(); return rc_; } } while (0)
+  });
   const unsigned blocks = (unsigned)((nreads + 127) / 128);
   int rc = MCX_OK;
   for (int i = 0; i < N && rc == MCX_OK; i++) {
@@ -884,39 +872,37 @@ static int grp_add_reads_pcr(mcx_group *G, int colour, const uint8_t *bases, con
     rc = cut_upload(*J[i], g, bases, quals, off, nreads, fq1, fq2, hp, true, paired, matedir);
     if (rc == MCX_OK) rc = cut_starts(*J[i]);
     if (rc != MCX_OK) break;
-    PCR_TRY(hipSetDevice(g->device));
-    PCR_TRY(hipMalloc((void **)&claims[i], (uint64_t)N * nreads));
-    PCR_TRY(hipEventCreateWithFlags(&claimed[i], hipEventDisableTiming));
+    HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipMalloc((void **)&claims[i], (uint64_t)N * nreads));
+    HIP_TRY(hipEventCreateWithFlags(&claimed[i], hipEventDisableTiming));
     hipLaunchKernelGGL(k_pcr_claim, dim3(blocks), dim3(128), 0, g->stream, (const uint64_t *)J[i]->d_node, (const uint32_t *)g->d_readstrt,
                        nreads, J[i]->pmask, claims[i] + (uint64_t)i * nreads);
-    PCR_TRY(hipGetLastError());
-    PCR_TRY(hipEventRecord(claimed[i], g->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(claimed[i], g->stream));
   }
-  if (rc != MCX_OK) { cleanup(); return rc; }
+  if (rc != MCX_OK) return rc;
   unsigned long long h_ndup = 0;
   const uint64_t nunits = J[0]->nunits;
   for (int j = 0; j < N; j++) {  // gather the claims, decide, commit
     mcx_graph *g = G->part[j];
-    PCR_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipSetDevice(g->device));
     for (int i = 0; i < N; i++)
       if (i != j) {
-        PCR_TRY(hipStreamWaitEvent(g->stream, claimed[i], 0));
-        PCR_TRY(hipMemcpyPeerAsync(claims[j] + (uint64_t)i * nreads, g->device, claims[i] + (uint64_t)i * nreads, G->part[i]->device, nreads, g->stream));
+        HIP_TRY(hipStreamWaitEvent(g->stream, claimed[i], 0));
+        HIP_TRY(hipMemcpyPeerAsync(claims[j] + (uint64_t)i * nreads, g->device, claims[i] + (uint64_t)i * nreads, G->part[i]->device, nreads, g->stream));
       }
     const uint64_t u_lo = nunits * (uint64_t)j / (uint64_t)N, u_hi = nunits * (uint64_t)(j + 1) / (uint64_t)N;
     hipLaunchKernelGGL(k_pcr_decide_claims, dim3((unsigned)((nunits + 255) / 256)), dim3(256), 0, g->stream, (const uint8_t *)claims[j],
-                       (uint32_t)N, nreads, nunits, J[j]->pmask, u_lo, u_hi, J[j]->d_keep, J[j]->d_ndup);
+                       (uint32_t)N, nreads, nunits, J[j]->pmask, u_lo, u_hi, J[j]->d_keep.p, J[j]->d_ndup.p);
     hipLaunchKernelGGL(k_pcr_commit, dim3(blocks), dim3(128), 0, g->stream, (const uint64_t *)J[j]->d_node, nreads, g->d_readstrt);
-    PCR_TRY(hipGetLastError());
-    if (j == 0) PCR_TRY(hipMemcpyAsync(&h_ndup, J[0]->d_ndup, 8, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipGetLastError());
+    if (j == 0) HIP_TRY(hipMemcpyAsync(&h_ndup, J[0]->d_ndup, 8, hipMemcpyDeviceToHost, g->stream));
   }
   for (int j = 0; j < N; j++) {  // (a shard's own claims must not be freed while another still copies them)
-    PCR_TRY(hipSetDevice(G->part[j]->device));
-    PCR_TRY(hipStreamSynchronize(G->part[j]->stream));
+    HIP_TRY(hipSetDevice(G->part[j]->device));
+    HIP_TRY(hipStreamSynchronize(G->part[j]->stream));
   }
   for (int j = 0; j < N && rc == MCX_OK; j++) rc = cut_finish(*J[j], colour);
-  cleanup();
-#undef PCR_TRY
   if (stats_accum) {
     if (paired) stats_accum->num_dup_pe_pairs += h_ndup; else stats_accum->num_dup_se_reads += h_ndup;
   }

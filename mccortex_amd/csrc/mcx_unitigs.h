@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void k_un_heads(TableView t, uint64_t n, const
   }
 }
 
-// the dense ids of `perm` -> key word w of their k-mers (the sort's next digit)
+// the items of `perm` (dense ids here, compacted entries in the export) -> key word w of their k-mers (the sort's next digit)
 __global__ __launch_bounds__(256) void k_un_keyword(TableView t, uint64_t nu, const uint64_t *slot_of, const uint64_t *perm, uint32_t w, uint64_t *dst)
 {
   for (uint64_t j = cl_first(); j < nu; j += cl_stride()) dst[j] = un_keyword(t, slot_of[perm[j]], w);

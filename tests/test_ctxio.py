@@ -406,6 +406,33 @@ def test_sort_records_and_sorted_check(mcx, k, ncols):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("ncols", [1, 2])
+@pytest.mark.parametrize("k", [31, 63, 95, 127])
+def test_sort_records_every_lsd_pass_matters(mcx, k, ncols):
+    """Keys that tie in every word: all 4^W combinations of four values per key word (random keys never tie in a
+    word, so they cannot see a pass in the wrong order or an unstable one), among random distinct keys."""
+    rng = np.random.default_rng(1000 * k + ncols)
+    W = (2 * k + 63) // 64
+    top_bits = 2 * k - 64 * (W - 1)
+    pools = [np.array([0, 1, (1 << (top_bits - 1)) - 1, 1 << (top_bits - 1)], dtype=np.uint64)]   # below bit top_bits
+    pools += [np.array([0, 1, 1 << 63, (1 << 64) - 1], dtype=np.uint64) for _ in range(W - 1)]
+    grid = np.stack(np.meshgrid(*pools, indexing="ij"), axis=-1).reshape(-1, W)
+    assert len(grid) == 4 ** W
+    n = 10000                                  # (_random_records repeats every key once: about 5000 distinct)
+    keys, covgs, edges, rec = _random_records(rng, k, ncols, n, W)
+    rs = 8 * W + 5 * ncols
+    a = np.frombuffer(rec, np.uint8).reshape(-1, rs).copy()
+    a[:len(grid), :8 * W] = grid.astype("<u8").view(np.uint8).reshape(len(grid), 8 * W)
+    _, first = np.unique(a[:, :8 * W].copy().view("<u8").reshape(-1, W), axis=0, return_index=True)   # distinct keys
+    a = a[np.sort(first)]
+    assert 4900 <= len(a) <= 5400
+    rec = a[rng.permutation(len(a))].tobytes()
+    got = mcx.sort_records(rec, k, ncols)
+    assert got == _np_sorted(rec, W, rs)
+    assert mcx.records_sorted(got, k, ncols) == -1
+
+
+@pytest.mark.gpu
 def test_kmer_covg_and_histogram(mcx, orc):
     k, ncols = 31, 3
     g0 = synth.genome(20000, 12)
@@ -685,3 +712,37 @@ def test_index_command_on_golden_files_cpu(mcx, name, maxk, tmp_path):
         bad.write_bytes(buf[:hs] + b"".join(recs))
         rc, _, err = run(maxk, "index", "-b", "4", str(bad))
         assert rc == 1 and "File is not sorted" in err
+
+
+@pytest.mark.gpu
+def test_intersect_reads_with_quality_cutoff(mcx, orc):
+    """Must-exist reads on one device WITH qualities and a cutoff (the command-line cases above read FASTA): the
+    upload's optional third buffer.  ctx_build.c:341-413 through the library calls the build command makes."""
+    k = 21
+    g0 = synth.genome(20000, 31)
+    ra = synth.reads(1500, 90, seed=1, g=g0)
+    rq = synth.reads(1200, 100, seed=3, g=g0, n_frac=0.05, lower_frac=0.1)
+    quals = np.random.default_rng(5).integers(33, 74, len(rq[0])).astype(np.uint8)
+    oi = orc.Graph(k, 1, 1 << 20)
+    oi.add_reads(0, *ra)
+    isec = oi.ctx_bytes(True)
+    hdr, hs = ctxio.read_header(isec)
+    keys, covgs, edges = ctxio.records(isec, hdr, hs)
+    og = orc.Graph(k, 1, 1 << 20)
+    for i in range(len(keys)):
+        og.add_isec_record(keys[i], int(covgs[i, 0]), int(edges[i, 0]))
+    og.set_must_exist(True)
+    ost = og.add_reads(0, *rq, quals=quals, fq_cutoff=43, hp_cutoff=0)
+    og.isec_finish()
+    plain = orc.Graph(k, 1, 1 << 20)                    # (the cutoff must matter for this input)
+    assert plain.add_reads(0, *rq).num_kmers_loaded > orc.Graph(k, 1, 1 << 20).add_reads(0, *rq, quals=quals, fq_cutoff=43).num_kmers_loaded
+    g = mcx.Graph(k, 2, 1 << 20, device=0)              # colour 1: the hidden holder of the intersection's edges
+    g.configure("intersect", 1)
+    g.add_records(isec[hs:], 1, [(0, 1)])
+    g.configure("must_exist", 1)
+    g.add_reads(0, *rq, quals=quals, fq_cutoff=43, hp_cutoff=0)
+    g.intersect_finish()
+    assert 0 < og.nkmers == g.nkmers
+    assert g.device_stats().num_kmers_loaded == ost.num_kmers_loaded
+    assert g.export(True) == og.body_bytes(True)
+    g.close()

@@ -704,3 +704,27 @@ def test_overfull_table_fails_fast(mcx, defer):
     assert ei.value.code == mcx.MCX_ERR_FULL
     assert time.perf_counter() - t0 < 30
     g.close()
+
+
+@pytest.mark.parametrize("k", [31, 63])
+def test_failing_export_sink_leaves_nothing_behind(mcx, orc, k):
+    """A sink that refuses its first chunk: the export returns MCX_ERR_SINK by way of its scope guards, and the
+    graph (its borrowed staging buffers and idle bins included) exports as before afterwards.  A host-side error
+    return.  (A sink that fails on its second call needs more than 64 MiB of records, 5 M k-mers: the oracle alone
+    takes longer than a test here may, so that variant is left out.)"""
+    from mccortex_amd.graph import MCX_ERR_SINK, SINK_FN
+    bases, offs = synth.reads(3000, 100, genome_len=20000, seed=k + 1, n_frac=0.05)
+    og = orc.Graph(k, 1, 1 << 20)
+    og.add_reads(0, bases, offs)
+    want = og.ctx_bytes(True)[og.header_size():]
+    g = mcx.Graph(k, 1, 1 << 20)
+    g.add_reads(0, bases, offs)
+    g.sync()
+    calls = []
+    refuse = SINK_FN(lambda _ctx, _ptr, n: calls.append(n) or 1)
+    for _ in range(2):  # (twice: the first failure must not have spoilt the second attempt either)
+        assert mcx.lib().mcx_graph_export(g.h, 1, refuse, None) == MCX_ERR_SINK
+        assert "export sink failed" in mcx.lib().mcx_last_error().decode()
+    assert len(calls) == 2 and calls[0] == len(want)
+    assert g.export(True) == want
+    g.close()
