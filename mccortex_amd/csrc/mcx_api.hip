@@ -436,7 +436,7 @@ extern "C" int mcx_graph_create_shard(mcx_graph **out, int kmer_size, int ncols,
   // overflow area behind the hash-addressed slots (mcx_kernels.h, ovf_start): 1/32 of the table,
   // at least one sub-table's worth
   uint64_t novf = std::max<uint64_t>(sub_slots, (nsub * sub_slots / 32 + sub_slots - 1) / sub_slots * sub_slots);
-  if (const char *e = getenv("MCX_OVERFLOW_SLOTS")) novf = strtoull(e, nullptr, 10) / kBucket * kBucket;  // tests
+  if (const char *e = getenv("MCX_OVERFLOW_SLOTS")) novf = std::max<uint64_t>(kBucket, strtoull(e, nullptr, 10) / kBucket * kBucket);  // tests (never empty: k_lds_insert spills unguarded)
   if (novf / kBucket >= (1ull << 32)) novf = ((1ull << 32) - 1) * kBucket;
   const uint64_t slots = nsub * sub_slots + novf;
   g->t.nmain = nsub * sub_slots;
