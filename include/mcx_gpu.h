@@ -458,6 +458,50 @@ int mcx_graph_reads_touch(mcx_graph *g, const uint8_t *bases, const uint64_t *re
 int mcx_graph_reads_touch_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes,
                                      const void *d_stream_off /* nreads+1 u64 */, uint64_t nreads, void *d_hit);
 
+/* `coverage` (src/commands/ctx_coverage.c; print_read_covg): what the table stores for the k-mers of reads.  The k-mers
+ * of a read are those of `reads` above (maximal runs of ACGTacgt of at least k bases, looked up by canonical key).  For
+ * a k-mer that is a key, colour c gives its coverage (clamped to 2^32 - 1, as the export clamps it) and its edge byte
+ * turned to the read's strand as fetch_node_edges turns it: where the read holds the reverse complement of the key the
+ * two nibbles change places and the bits inside a nibble stay.  Every other start position -- an absent k-mer, a window
+ * over an N or a separator, the last k - 1 positions of a read -- gives 0.  The answer is a function of the table's
+ * contents and the reads alone, not of the table's size or load, the chunking or the "grid" knob.  The table is only
+ * read.
+ *   mcx_graph_coverage   takes the layout of mcx_graph_add_reads.  covg is [ncols][nbases] and edges, if not NULL, the
+ *       same shape, with nbases = read_offsets[nreads]: index p of a colour holds the k-mer that starts at bases[p] (the
+ *       stream's separators do not appear).  Flushes pending inserts first.  Synchronous.  The reads go through the
+ *       pinned staging buffers as ASCII in chunks ("reads_chunk" of mcx_graph_configure lowers their size, as for
+ *       mcx_graph_reads_touch: a test knob); a read longer than a chunk is probed in pieces that overlap by k - 1
+ *       bases, so every k-mer starts in exactly one piece.  The batch's arrays are held in HBM until they are copied
+ *       out: 4 (+ 1 with edges) bytes per colour and base; MCX_ERR_NOMEM when that does not fit.  stats, if given, is
+ *       added to.  nreads == 0 is MCX_OK.
+ *   mcx_graph_coverage_stream_dev   the same over a stream in HBM with the layout of mcx_graph_add_stream_dev (ASCII,
+ *       16-byte aligned, any non-base byte separates reads).  d_covg is [ncols][pitch] 32-bit words and d_edges, if not
+ *       NULL, [ncols][pitch] bytes, both 16-byte aligned and indexed by stream position; pitch is a multiple of 64 and
+ *       at least nbytes.  Positions [0, nbytes) of every colour are written, zeros included (and some of the padding
+ *       behind them), so nothing needs clearing between calls.  Asynchronous on the handle's stream; counts nothing.
+ *   mcx_graph_coverage_text   the value lines of the command, written on the device after all pieces of the batch have
+ *       been probed (a line is never cut by a chunk seam).  For every read in input order and every colour in ascending
+ *       order: the edges line with MCX_COVERAGE_EDGES (two lower-case hex characters per k-mer, edges_to_char, separated
+ *       by one space), the degree line with MCX_COVERAGE_DEGREES (one of "./[\-{]}X" per k-mer, by min(indegree, 2) and
+ *       min(outdegree, 2)), then the coverage line ("%2u" of the first value, " %2u" of every further one).  A line has
+ *       klen = max(len - k + 1, 0) values and ends in '\n'; klen = 0 gives a bare '\n'.  The text reaches `sink` in
+ *       consecutive byte ranges, like mcx_graph_export's records; line_off, if not NULL, receives
+ *       nreads * ncols * lines-per-colour + 1 offsets into it.  HBM: 5 * ncols bytes per base of the batch plus the
+ *       text, which is sized by a scan of the line lengths; MCX_ERR_NOMEM when that does not fit.
+ * Refusals (MCX_ERR_ARG): a graph split over devices, a handle in intersect mode, unknown flags, edge or degree lines
+ * asked of a call that gathered no edges. */
+/* the sink of the calls that hand out bytes in consecutive ranges (this one, mcx_graph_export, mcx_graph_unitigs); != 0 stops the call */
+typedef int (*mcx_sink_fn)(void *ctx, const void *records, size_t nbytes);
+typedef struct { uint64_t num_reads, num_kmers, num_kmers_found; } mcx_coverage_stats;
+enum { MCX_COVERAGE_EDGES = 1, MCX_COVERAGE_DEGREES = 2 };
+int mcx_graph_coverage(mcx_graph *g, const uint8_t *bases, const uint64_t *read_offsets, uint64_t nreads,
+                       uint32_t *covg /* [ncols][nbases] */, uint8_t *edges /* same shape, or NULL */,
+                       mcx_coverage_stats *stats_accum /* optional, += */);
+int mcx_graph_coverage_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes, void *d_covg /* [ncols][pitch] u32 */,
+                                  void *d_edges /* [ncols][pitch] u8, or NULL */, uint64_t pitch);
+int mcx_graph_coverage_text(mcx_graph *g, const uint8_t *bases, const uint64_t *read_offsets, uint64_t nreads, uint32_t flags,
+                            mcx_sink_fn sink, void *ctx, uint64_t *line_off, mcx_coverage_stats *stats_accum /* optional, += */);
+
 /* `inferedges`: infer_kmer_edges (src/tools/infer_edges.c) for every record of `recs` (.ctx body
  * layout, ncols == the graph's colours) against the k-mers loaded into the graph.  Each edge that some
  * colour lacks (default, --all) or that some colour has and another lacks (MCX_INFER_POP, --pop)
@@ -589,7 +633,6 @@ void *mcx_graph_stream(mcx_graph *g);
  * ncols x u8 edges; src/graph/graph_writer.c:116-127) to `sink` in chunks.
  * sorted != 0 orders records by key (hash_table_sorted, hash_table.c:362-374),
  * which is the only order in which the reference output is reproducible. */
-typedef int (*mcx_sink_fn)(void *ctx, const void *records, size_t nbytes);
 int mcx_graph_export(mcx_graph *g, int sorted, mcx_sink_fn sink, void *ctx);
 
 /* `unitigs` (src/commands/ctx_unitigs.c): every unitig of the decomposition above as text, written by kernels

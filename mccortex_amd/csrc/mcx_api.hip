@@ -34,6 +34,7 @@
 #include "mcx_pop.h"
 #include "mcx_subgraph.h"
 #include "mcx_reads.h"
+#include "mcx_coverage.h"
 
 using namespace mcx;
 
@@ -3907,6 +3908,219 @@ extern "C" int mcx_graph_reads_touch(mcx_graph *g, const uint8_t *bases, const u
     stats_accum->num_kmers += h[0];
     stats_accum->num_kmers_found += h[1];
   }
+  return MCX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// coverage (ctx_coverage.c): what the table stores for the k-mers of reads -- mcx_coverage.h
+// ---------------------------------------------------------------------------
+static int coverage_begin(mcx_graph *g)
+{
+  if (!g) return fail(MCX_ERR_ARG, "null graph");
+  if (g->as_group || g->group || g->t.lbo || g->own_lbo)
+    return fail(MCX_ERR_ARG, "coverage needs the whole table on one device, not a graph split over devices (a read's k-mers are on every shard)");
+  if (g->hidden >= 0) return fail(MCX_ERR_ARG, "coverage does not take a graph in intersect mode");
+  HIP_TRY(hipSetDevice(g->device));
+  if (!g->d_rt_cnt) {
+    HIP_TRY(hipMalloc((void **)&g->d_rt_cnt, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), g->stream));
+  }
+  return flush_deferred(g);  // the lookups see every insert made so far
+}
+
+// pass A over one stream (positions [0, nbytes)) into arrays of `pitch` positions per colour, on the handle's stream
+static int coverage_probe(mcx_graph *g, const uint8_t *d_stream, uint64_t nbytes, uint32_t *d_covg, uint8_t *d_edges, uint64_t pitch)
+{
+  hipStream_t st = g->stream;
+  const StreamArgs a = make_args(g, StreamLaunch{d_stream, nbytes, 0, nbytes, nullptr});
+  if (a.ntiles) GRID_LAUNCH_W(k_cv_probe, a.ntiles * (uint64_t)kThreads, a, g->t, (uint32_t)g->ncols, pitch, d_covg, d_edges, g->d_rt_cnt);
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_coverage_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes, void *d_covg, void *d_edges, uint64_t pitch)
+{
+  int rc = coverage_begin(g);
+  if (rc != MCX_OK) return rc;
+  if (((uintptr_t)d_stream & 15) != 0) return fail(MCX_ERR_ARG, "stream must be 16-byte aligned");
+  if (((uintptr_t)d_covg & 15) != 0 || ((uintptr_t)d_edges & 15) != 0) return fail(MCX_ERR_ARG, "coverage: the output arrays must be 16-byte aligned");
+  if (!nbytes) return MCX_OK;
+  if (!d_stream || !d_covg) return fail(MCX_ERR_ARG, "null stream buffers");
+  if ((pitch & 63) != 0 || pitch < nbytes) return fail(MCX_ERR_ARG, "coverage: the pitch (%llu) must be a multiple of 64 and hold the stream's %llu positions",
+                                                        (unsigned long long)pitch, (unsigned long long)nbytes);
+  return coverage_probe(g, (const uint8_t *)d_stream, nbytes, (uint32_t *)d_covg, (uint8_t *)d_edges, pitch);
+}
+
+// what a batch of host reads leaves on the device: the arrays indexed by base position (off[0] is position 0), `pitch`
+// positions per colour, and the reads' offsets
+struct CvBatch {
+  uint64_t pitch = 0;
+  DevBuf<uint32_t> covg;
+  DevBuf<uint8_t> edges;
+  DevBuf<uint64_t> off;
+  unsigned long long cnt[2] = {0, 0};
+};
+
+// Host reads through the pinned staging buffers as ASCII, chunked as mcx_graph_reads_touch chunks them: whole reads each
+// followed by a separator, or one piece of a read that does not fit a chunk; consecutive pieces overlap by k - 1 bases
+// and a piece owns the k-mers that start in it, that is all its positions but the last k - 1 (the last piece owns all
+// of its own).  A chunk is probed into scratch arrays indexed by its stream position and placed from there into the
+// batch's.  Synchronous.
+static int coverage_batch(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, bool want_edges, CvBatch &B)
+{
+  int rc = ensure_stage(g);
+  if (rc != MCX_OK) return rc;
+  hipStream_t st = g->stream;
+  const uint64_t ncols = (uint64_t)g->ncols, nbases = off[nreads] - off[0];
+  B.pitch = std::max<uint64_t>(64, (nbases + 63) / 64 * 64);
+  // layout of a staging buffer: [0, C) stream | offsets (R + 1); R = C / 16 reads at most
+  const uint64_t S = g->stage_alloc;
+  uint64_t C = (std::min<uint64_t>(kStageBytes, g->reads_chunk ? g->reads_chunk : ~0ull) + 63) / 64 * 64;
+  if (S < 1024) return fail(MCX_ERR_ARG, "coverage: the staging buffers (%llu bytes) are too small", (unsigned long long)S);
+  C = std::max<uint64_t>(256, std::min<uint64_t>(C, ((S - 64) * 2 / 3) & ~63ull));
+  const uint64_t R = C / 16, off_at = C;
+  if (off_at + 8 * (R + 1) > S) return fail(MCX_ERR_HIP, "coverage: internal error in the staging layout");
+  const uint64_t spitch = C;  // (a multiple of 64)
+  DevBuf<uint32_t> scovg;
+  DevBuf<uint8_t> sedges;
+  HIP_TRY(B.covg.alloc(ncols * B.pitch));
+  if (want_edges) HIP_TRY(B.edges.alloc(ncols * B.pitch));
+  HIP_TRY(B.off.alloc(nreads + 1));
+  HIP_TRY(scovg.alloc(ncols * spitch));
+  if (want_edges) HIP_TRY(sedges.alloc(ncols * spitch));
+  HIP_TRY(hipMemcpyAsync(B.off, off, 8 * (nreads + 1), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
+  const uint64_t k1 = (uint64_t)g->k - 1;
+  uint64_t r = 0, r_pos = 0;  // next read, first base of it that the next piece starts with
+  auto run = [&]() -> int {
+    while (r < nreads) {
+      const int b = g->cur;
+      g->cur = (g->cur + 1) % mcx_graph::kStageBufs;
+      HIP_TRY(hipEventSynchronize(g->ev[b]));  // previous use of this buffer finished
+      uint8_t *hs = g->h_stage[b];
+      uint64_t *ho = reinterpret_cast<uint64_t *>(hs + off_at);
+      uint64_t L = 0, n = 0, shift = 0, own = ~0ull;
+      const uint64_t r0 = r;
+      ho[0] = 0;
+      while (r < nreads && n < R) {
+        const uint64_t len = off[r + 1] - off[r];
+        if (r_pos == 0 && len + 1 <= C - L) {
+          if (len) memcpy(hs + L, bases + off[r], len);
+          L += len;
+          hs[L++] = '\n';
+          ho[++n] = L;
+          r++;
+        } else if (L == 0) {  // a read longer than a chunk: a piece on its own
+          const uint64_t take = std::min(len - r_pos, C - 1);
+          memcpy(hs, bases + off[r] + r_pos, take);
+          L = take;
+          hs[L++] = '\n';
+          ho[++n] = L;
+          shift = r_pos;
+          if (r_pos + take == len) { r++; r_pos = 0; }
+          else { own = take - k1; r_pos += take - k1; }
+          break;
+        } else {
+          break;
+        }
+      }
+      uint8_t *ds = g->d_stage[b];
+      HIP_TRY(hipMemcpyAsync(ds, hs, L, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(ds + off_at, ho, 8 * (n + 1), hipMemcpyHostToDevice, st));
+      int rc2 = coverage_probe(g, ds, L, scovg, sedges, spitch);
+      if (rc2 != MCX_OK) return rc2;
+      GRID_LAUNCH(k_cv_place, L, reinterpret_cast<const uint64_t *>(ds + off_at), n, (const uint64_t *)B.off.p, r0, shift, own, (uint32_t)ncols,
+                  (const uint32_t *)scovg.p, (const uint8_t *)sedges.p, spitch, B.covg.p, B.edges.p, B.pitch);
+      HIP_TRY(hipEventRecord(g->ev[b], st));
+    }
+    HIP_TRY(hipMemcpyAsync(B.cnt, g->d_rt_cnt, sizeof(B.cnt), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MCX_OK;
+  };
+  rc = run();
+  if (rc != MCX_OK) (void)hipStreamSynchronize(st);  // before the scratch goes
+  return rc;
+}
+
+static void coverage_add_stats(mcx_coverage_stats *s, uint64_t nreads, const CvBatch &B)
+{
+  if (!s) return;
+  s->num_reads += nreads;
+  s->num_kmers += B.cnt[0];
+  s->num_kmers_found += B.cnt[1];
+}
+
+extern "C" int mcx_graph_coverage(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, uint32_t *covg, uint8_t *edges,
+                                  mcx_coverage_stats *stats_accum)
+{
+  int rc = coverage_begin(g);
+  if (rc != MCX_OK) return rc;
+  if (!nreads) return MCX_OK;
+  if (!off || !covg) return fail(MCX_ERR_ARG, "null read buffers");
+  if (!bases && off[nreads] != off[0]) return fail(MCX_ERR_ARG, "null read buffers");
+  CvBatch B;
+  if ((rc = coverage_batch(g, bases, off, nreads, edges != nullptr, B)) != MCX_OK) return rc;
+  // host arrays: off[nreads] positions per colour, position p = the k-mer that starts at bases[p]
+  const uint64_t hp = off[nreads], n = off[nreads] - off[0];
+  for (uint64_t c = 0; c < (uint64_t)g->ncols; c++) {
+    memset(covg + c * hp, 0, 4 * off[0]);
+    if (n) HIP_TRY(hipMemcpy(covg + c * hp + off[0], B.covg.p + c * B.pitch, 4 * n, hipMemcpyDeviceToHost));
+    if (edges) {
+      memset(edges + c * hp, 0, off[0]);
+      if (n) HIP_TRY(hipMemcpy(edges + c * hp + off[0], B.edges.p + c * B.pitch, n, hipMemcpyDeviceToHost));
+    }
+  }
+  coverage_add_stats(stats_accum, nreads, B);
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_coverage_text(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, uint32_t flags, mcx_sink_fn sink,
+                                       void *ctx, uint64_t *line_off, mcx_coverage_stats *stats_accum)
+{
+  int rc = coverage_begin(g);
+  if (rc != MCX_OK) return rc;
+  if (flags & ~(uint32_t)(MCX_COVERAGE_EDGES | MCX_COVERAGE_DEGREES)) return fail(MCX_ERR_ARG, "coverage: unknown flags 0x%x", flags);
+  if (!nreads) { if (line_off) line_off[0] = 0; return MCX_OK; }
+  if (!off || !sink) return fail(MCX_ERR_ARG, "null read buffers");
+  if (!bases && off[nreads] != off[0]) return fail(MCX_ERR_ARG, "null read buffers");
+  CvBatch B;
+  if ((rc = coverage_batch(g, bases, off, nreads, flags != 0, B)) != MCX_OK) return rc;
+  if (flags && !B.edges.p) return fail(MCX_ERR_ARG, "coverage: edge or degree lines asked of a call that gathered no edges");
+  hipStream_t st = g->stream;
+  const uint32_t lpc = 1 + ((flags & MCX_COVERAGE_EDGES) ? 1 : 0) + ((flags & MCX_COVERAGE_DEGREES) ? 1 : 0);
+  const uint64_t nlines = nreads * (uint64_t)g->ncols * lpc;
+  const CvText x{B.off.p, nreads, g->k, (uint32_t)g->ncols, flags, lpc, B.covg.p, B.edges.p, B.pitch};
+  DevBuf<uint64_t> len, loff;
+  HIP_TRY(len.alloc(nlines + 1));
+  HIP_TRY(loff.alloc(nlines + 1));
+  HIP_TRY(hipMemsetAsync(len.p + nlines, 0, 8, st));
+  GRID_LAUNCH(k_cv_len, nreads * (uint64_t)g->ncols, x, len.p);
+  if ((rc = device_scan(st, (const uint64_t *)len.p, loff.p, nlines + 1)) != MCX_OK) return rc;
+  uint64_t total = 0;
+  HIP_TRY(hipMemcpy(&total, loff.p + nlines, 8, hipMemcpyDeviceToHost));
+  len.release();
+  DevBuf<uint8_t> text;  // sized by the scan
+  HIP_TRY(text.alloc(std::max<uint64_t>(total, 1)));
+  GRID_LAUNCH(k_cv_emit, nlines * 64, x, (const uint64_t *)loff.p, (uint64_t)0, nlines, text.p);
+  if (line_off) HIP_TRY(hipMemcpyAsync(line_off, loff.p, 8 * (nlines + 1), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));  // the text is complete, the staging buffers are ours
+  HIP_TRY(hipStreamSynchronize(g->cstream));
+  // chunk i + 1 is copied out while chunk i is with the sink
+  const uint64_t chunk = std::min<uint64_t>(kStageBytes, g->stage_alloc) & ~15ull;
+  auto fetch = [&](uint64_t c0, int b) -> int {
+    HIP_TRY(hipMemcpyAsync(g->h_stage[b], text.p + c0, std::min(total, c0 + chunk) - c0, hipMemcpyDeviceToHost, g->cstream));
+    HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
+    return MCX_OK;
+  };
+  if (total) rc = fetch(0, 0);
+  int b = 0;
+  for (uint64_t c0 = 0; c0 < total && rc == MCX_OK; c0 += chunk, b ^= 1) {
+    if (c0 + chunk < total && (rc = fetch(c0 + chunk, b ^ 1)) != MCX_OK) break;
+    HIP_TRY(hipEventSynchronize(g->ev_copy[b]));
+    if (sink(ctx, g->h_stage[b], (size_t)(std::min(total, c0 + chunk) - c0)) != 0) rc = fail(MCX_ERR_SINK, "coverage sink failed");
+  }
+  (void)hipStreamSynchronize(g->cstream);  // leave nothing in flight on the staging buffers, nor on the text
+  if (rc != MCX_OK) return rc;
+  coverage_add_stats(stats_accum, nreads, B);
   return MCX_OK;
 }
 

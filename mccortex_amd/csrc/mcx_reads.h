@@ -25,11 +25,15 @@ namespace mcx {
 // stretch to tens of thousands.
 constexpr uint64_t kRtLongStarts = 4096;
 
-// The sink of rt_probe that `reads` uses: hit16 has position P0 + j at bit j.  Another user of the walk (a per-k-mer
-// coverage lookup, say) passes a sink of its own to rt_probe from a kernel of its own.
+// What a lane hands to the sink of rt_probe for its 16 start positions P0 .. P0 + 15: hit16 has position P0 + j at bit
+// j.  A sink that sets kSlots also receives, per position, the slot of the k-mer (kNoSlot where hit16 has no bit) and
+// in o16 bit j the orientation canonical<W> returned for it (1: the key is the reverse complement of the read's k-mer);
+// for a sink that does not, the two are not computed (slot[] holds nothing) and the walk is the one `reads` always had.
+// The sink of `reads`: one 16-bit word per lane.  `coverage` passes a sink of its own (mcx_coverage.h).
 struct RtMaskSink {
+  static constexpr bool kSlots = false;
   uint16_t *hit;
-  __device__ __forceinline__ void operator()(uint64_t P0, uint32_t hit16) const { hit[P0 >> 4] = (uint16_t)hit16; }
+  __device__ __forceinline__ void operator()(uint64_t P0, uint32_t hit16, const uint64_t (&)[16], uint32_t) const { hit[P0 >> 4] = (uint16_t)hit16; }
 };
 
 constexpr int kRtBatch = 4;  // lookups in flight per lane (divides 16), as k_stream's kBatch: the first probes are independent loads
@@ -44,6 +48,16 @@ template <int W> __device__ __forceinline__ bool rt_found(const TableView &t, co
   if (W == 1 && cur == (key.w[0] | kFlag)) return true;
   uint32_t novel = 0, full = 0;
   return find_or_insert_rec<W>(t, key, true, novel, full) != kNoSlot;  // must_exist: read-only
+}
+
+// The slot of `key` (kNoSlot: absent), given the word `cur` read at its first slot s0: rt_found's two shortcuts, with
+// the slot kept.
+template <int W> __device__ __forceinline__ uint64_t rt_find(const TableView &t, const Kmer<W> &key, uint64_t cur, uint64_t s0)
+{
+  if (cur == 0) return kNoSlot;
+  if (W == 1 && cur == (key.w[0] | kFlag)) return s0;
+  uint32_t novel = 0, full = 0;
+  return find_or_insert_rec<W>(t, key, true, novel, full);  // must_exist: read-only
 }
 
 // cnt[0] += k-mer occurrences probed, cnt[1] += occurrences whose k-mer is in the table.  Every lane of every tile in
@@ -73,7 +87,10 @@ __device__ __forceinline__ void rt_probe(const StreamArgs &a, const TableView &t
     uint32_t ok16, nok16;
     lane_masks_wide(s_inv, pl, k, ok16, nok16);
     ok16 &= ((0x10000u >> j_lo) - 1u) & ~((0x10000u >> j_hi) - 1u);
-    uint32_t hit16 = 0;
+    uint32_t hit16 = 0, o16 = 0;
+    uint64_t slot[kPosPerLane];
+    if constexpr (Sink::kSlots)
+      for (int j = 0; j < kPosPerLane; j++) slot[j] = kNoSlot;
     if (ok16) {
       Kmer<W> fw, rc;
       fw.w[0] = code_win64(s_code, pl) >> (64 - 2 * topb);
@@ -82,7 +99,7 @@ __device__ __forceinline__ void rt_probe(const StreamArgs &a, const TableView &t
       const uint64_t feed = code_win64(s_code, pl + (uint32_t)k);
       for (int j0 = 0; j0 < kPosPerLane; j0 += kRtBatch) {
         Kmer<W> key[kRtBatch];
-        uint64_t cur[kRtBatch];
+        uint64_t cur[kRtBatch], s0[kRtBatch];
         bool ov[kRtBatch];
 #pragma unroll
         for (int b = 0; b < kRtBatch; b++) {  // issue the first probe of every k-mer of the batch before looking at any
@@ -92,7 +109,9 @@ __device__ __forceinline__ void rt_probe(const StreamArgs &a, const TableView &t
           if (ov[b]) {
             uint32_t o;
             key[b] = canonical<W>(fw, rc, o);
-            cur[b] = __hip_atomic_load(key_ptr(t, key_slot<W>(t, key[b])), MCX_RLX, MCX_AGENT);
+            const uint64_t s = key_slot<W>(t, key[b]);
+            cur[b] = __hip_atomic_load(key_ptr(t, s), MCX_RLX, MCX_AGENT);
+            if constexpr (Sink::kSlots) { s0[b] = s; o16 |= o << j; }
           }
           const uint32_t nuc_next = (uint32_t)(feed >> (62 - 2 * j)) & 3u;
           kmer_push<W>(fw, nuc_next, k);
@@ -103,12 +122,17 @@ __device__ __forceinline__ void rt_probe(const StreamArgs &a, const TableView &t
         for (int b = 0; b < kRtBatch; b++)
           if (ov[b]) {
             n_occ++;
-            if (rt_found<W>(t, key[b], cur[b])) hit16 |= 1u << (j0 + b);
+            if constexpr (Sink::kSlots) {
+              slot[j0 + b] = rt_find<W>(t, key[b], cur[b], s0[b]);
+              if (slot[j0 + b] != kNoSlot) hit16 |= 1u << (j0 + b);
+            } else {
+              if (rt_found<W>(t, key[b], cur[b])) hit16 |= 1u << (j0 + b);
+            }
           }
       }
     }
     n_hit += (unsigned long long)__popc(hit16);
-    sink(P0, hit16);
+    sink(P0, hit16, slot, o16);
   }
   block_add(&cnt[0], n_occ);
   block_add(&cnt[1], n_hit);

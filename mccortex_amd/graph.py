@@ -25,6 +25,7 @@ SYMBOLS = [
     "mcx_graph_unitigs", "mcx_graph_unitigs_dev", "mcx_graph_pop_bubbles",
     "mcx_graph_subgraph_begin", "mcx_graph_subgraph_seed_reads", "mcx_graph_subgraph_seed_stream_dev", "mcx_graph_subgraph_finish",
     "mcx_graph_reads_touch", "mcx_graph_reads_touch_stream_dev",
+    "mcx_graph_coverage", "mcx_graph_coverage_stream_dev", "mcx_graph_coverage_text",
 ]
 
 
@@ -93,6 +94,14 @@ class TouchStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class CoverageStats(C.Structure):
+    """mcx_coverage_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("num_reads", "num_kmers", "num_kmers_found")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class UnitigsStats(C.Structure):
     """mcx_unitigs_stats"""
     _fields_ = [(n, C.c_uint64) for n in ("num_unitigs", "num_kmers", "num_bytes", "num_cycles")]
@@ -112,6 +121,7 @@ UNITIGS_POINTS = 1
 RECORDS_MUST_EXIST = 1
 INFER_POP, INFER_PRESENCE_COVG = 1, 2
 SUBGRAPH_UNITIGS, SUBGRAPH_INVERT = 1, 2
+COVERAGE_EDGES, COVERAGE_DEGREES = 1, 2
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 
 
@@ -159,6 +169,9 @@ def lib():
     L.mcx_graph_subgraph_finish.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(SubgraphStats)]
     L.mcx_graph_reads_touch.argtypes = [vp, vp, vp, C.c_uint64, vp, C.POINTER(TouchStats)]
     L.mcx_graph_reads_touch_stream_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp]
+    L.mcx_graph_coverage.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(CoverageStats)]
+    L.mcx_graph_coverage_stream_dev.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64]
+    L.mcx_graph_coverage_text.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, SINK_FN, vp, vp, C.POINTER(CoverageStats)]
     L.mcx_graph_unitigs.argtypes = [vp, C.c_int, C.c_uint32, SINK_FN, vp, C.POINTER(UnitigsStats)]
     L.mcx_graph_unitigs_dev.argtypes = [vp, C.POINTER(UnitigsArrays), C.POINTER(UnitigsStats)]
     L.mcx_graph_infer_edges.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, u64p]
@@ -539,6 +552,47 @@ class Graph:
     def reads_touch_stream_dev(self, d_stream, nbytes, d_stream_off, nreads, d_hit):
         """the same over a stream in HBM (torch tensors or addresses); asynchronous on the graph's stream"""
         _check(self.L.mcx_graph_reads_touch_stream_dev(self.h, _ptr(d_stream), int(nbytes), _ptr(d_stream_off), int(nreads), _ptr(d_hit)))
+
+    def coverage(self, bases, offsets, edges=False, stats=None):
+        """`coverage` (ctx_coverage.c, print_read_covg): (np.uint32[ncols, nbases], np.uint8[ncols, nbases] or None,
+        CoverageStats) with nbases = offsets[-1] -- index p of a colour holds the coverage (and the edges, turned to the
+        read's strand) of the k-mer that starts at bases[p], 0 where none does or it is not in the graph.  `stats`, if
+        given, is added to."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nreads = max(len(offsets) - 1, 0)
+        nbases = int(offsets[-1]) if len(offsets) else 0
+        covg = np.zeros((self.ncols, nbases), dtype=np.uint32)
+        edg = np.zeros((self.ncols, nbases), dtype=np.uint8) if edges else None
+        st = stats if stats is not None else CoverageStats()
+        _check(self.L.mcx_graph_coverage(self.h, _ptr(bases), _ptr(offsets), nreads, _ptr(covg), _ptr(edg) if edges else None, C.byref(st)))
+        return covg, edg, st
+
+    def coverage_stream_dev(self, d_stream, nbytes, d_covg, d_edges, pitch):
+        """the same over a stream in HBM (torch tensors or addresses) into d_covg[ncols, pitch] (32-bit) and, unless
+        None, d_edges[ncols, pitch] (bytes), indexed by stream position; asynchronous on the graph's stream"""
+        _check(self.L.mcx_graph_coverage_stream_dev(self.h, _ptr(d_stream), int(nbytes), _ptr(d_covg),
+                                                    _ptr(d_edges) if d_edges is not None else None, int(pitch)))
+
+    def coverage_text(self, bases, offsets, edges=False, degrees=False, stats=None):
+        """the value lines of `coverage`, written on the device: (bytes, np.uint64 line_off, CoverageStats).  Per read and
+        colour the edges line (if `edges`), the degree line (if `degrees`) and the coverage line; line i is
+        text[line_off[i]:line_off[i + 1]]"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nreads = max(len(offsets) - 1, 0)
+        flags = (COVERAGE_EDGES if edges else 0) | (COVERAGE_DEGREES if degrees else 0)
+        line_off = np.zeros(nreads * self.ncols * (1 + bool(edges) + bool(degrees)) + 1, dtype=np.uint64)
+        parts = []
+
+        def sink(_ctx, ptr, n):
+            parts.append(C.string_at(ptr, n))
+            return 0
+
+        st = stats if stats is not None else CoverageStats()
+        _check(self.L.mcx_graph_coverage_text(self.h, _ptr(bases), _ptr(offsets), nreads, flags, SINK_FN(sink), None, _ptr(line_off),
+                                              C.byref(st)))
+        return b"".join(parts), line_off, st
 
     def subgraph(self, seeds, dist=0, invert=False, unitigs=False):
         """`subgraph` (ctx_subgraph.c): keep the k-mers within `dist` edges of the k-mers of `seeds` (a list of str or
