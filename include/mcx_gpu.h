@@ -174,8 +174,10 @@ int mcx_graph_capacity(const mcx_graph *g, uint64_t *slots, uint64_t *bytes);
  * contig split (src/basic/seq_reader.c:61-172), rolling k-mers, canonical key,
  * find-or-insert, coverage +1, edge OR (src/tools/build_graph.c:122-150).
  *   bases          concatenated read bases (ASCII, any case), no separators
- *   quals          NULL, or quality bytes in the same layout (only read when
- *                  fq_cutoff_abs > 0)
+ *   quals          NULL, or quality bytes in the same layout.  They decide under a
+ *                  cutoff; without one only a byte >= 128 does (a negative `char`
+ *                  ends a contig in seq_contig_end2 whatever the cutoff,
+ *                  seq_reader.c:148-149): the batch is scanned for one
  *   read_offsets   nreads+1 offsets into bases/quals
  *   fq_cutoff_abs  prefs.fq_cutoff + FASTQ offset, 0 = off (build_graph.c:203-206)
  *   hp_cutoff      homopolymer cutoff, 0 = off

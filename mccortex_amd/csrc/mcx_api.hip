@@ -2584,6 +2584,19 @@ static int add_reads_packed(mcx_graph *g, int colour, const uint8_t *bases, cons
   return MCX_OK;
 }
 
+// Do the qualities of a batch change what is loaded?  With a cutoff, yes.  Without one only where a byte has its top
+// bit set: the reference holds qualities as `char` and ends a contig at `qual < cutoff` (seq_contig_end2,
+// seq_reader.c:148-149), which a negative char satisfies even for cutoff 0; seq_contig_start looks at qualities only
+// under a cutoff (seq_reader.c:85).  The kernels restate both, so such a batch takes the -Q / -H path with cutoff 0.
+static bool quals_matter(const uint8_t *quals, const uint64_t *off, uint64_t nreads, uint8_t fq1, uint8_t fq2)
+{
+  if (!quals || !nreads) return false;
+  if (fq1 > 0 || fq2 > 0) return true;
+  uint8_t any = 0;
+  for (const uint8_t *p = quals + off[0], *const e = quals + off[nreads]; p < e; p++) any |= *p;
+  return (any & 0x80u) != 0;
+}
+
 extern "C" int mcx_graph_add_reads(mcx_graph *g, int colour, const uint8_t *bases, const uint8_t *quals,
                                    const uint64_t *off, uint64_t nreads, uint8_t fq_cutoff_abs,
                                    uint8_t hp_cutoff, mcx_load_stats *stats_accum)
@@ -2607,7 +2620,7 @@ extern "C" int mcx_graph_add_reads(mcx_graph *g, int colour, const uint8_t *base
   if (!nreads) return MCX_OK;
   if (colour >= g->ncols_vis) return fail(MCX_ERR_ARG, "colour %d is the intersection colour", colour);
   if (g->must_exist) return add_reads_must_exist(g, colour, bases, quals, off, nreads, fq_cutoff_abs, hp_cutoff);
-  if ((fq_cutoff_abs > 0 && quals) || hp_cutoff > 0)
+  if (quals_matter(quals, off, nreads, fq_cutoff_abs, fq_cutoff_abs) || hp_cutoff > 0)
     return add_reads_qh(g, colour, bases, quals, off, nreads, fq_cutoff_abs, hp_cutoff);
 
   int rc = ensure_stage(g);
@@ -2727,7 +2740,7 @@ static int add_reads_must_exist(mcx_graph *g, int colour, const uint8_t *bases, 
   std::vector<uint64_t> rel(nreads + 1);
   for (uint64_t i = 0; i <= nreads; i++) rel[i] = off[i] - base0;
   if (d_bases.alloc(nb + 16) != hipSuccess || d_off.alloc(nreads + 1) != hipSuccess ||
-      (quals && fq > 0 && d_quals.alloc(nb + 16) != hipSuccess)) {
+      (quals_matter(quals, off, nreads, fq, fq) && d_quals.alloc(nb + 16) != hipSuccess)) {
     (void)hipGetLastError();
     return fail(MCX_ERR_NOMEM, "out of device memory for a read batch");
   }
@@ -2811,7 +2824,7 @@ static int cut_upload(CutJob &J, mcx_graph *g, const uint8_t *bases, const uint8
   HIP_TRY(hipSetDevice(g->device));
   std::vector<uint64_t> rel(nreads + 1);
   for (uint64_t i = 0; i <= nreads; i++) rel[i] = off[i] - base0;
-  const bool use_q = quals && (fq1 > 0 || fq2 > 0);
+  const bool use_q = quals_matter(quals, off, nreads, fq1, fq2);
   HIP_TRY(J.d_bases.alloc(J.nb + 16));
   if (use_q) HIP_TRY(J.d_quals.alloc(J.nb + 16));
   HIP_TRY(J.d_off.alloc(nreads + 1));

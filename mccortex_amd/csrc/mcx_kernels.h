@@ -1155,7 +1155,7 @@ __global__ void k_qh_contigs(const uint8_t *bases, const uint8_t *quals, const u
   if (keep && !keep[r]) { if (!pass) out_sizes[r] = 0; return; }
   const uint32_t qcut = ((uint32_t)r & pmask) ? qcut2 : qcut1;
   const uint8_t *seq = bases + off[r];
-  const uint8_t *qual = (quals && qcut > 0) ? quals + off[r] : nullptr;
+  const uint8_t *qual = quals ? quals + off[r] : nullptr;  // (uploaded only when they matter: quals_matter)
   const uint64_t len = off[r + 1] - off[r];
   uint64_t cs, ce, search = 0, w = pass ? out_off[r] : 0;
   while ((cs = qh_contig_start(seq, len, qual, search, (uint64_t)k, qcut, hcut)) < len) {
@@ -1217,7 +1217,7 @@ __global__ void k_pcr_starts(TableView t, const uint8_t *bases, const uint8_t *q
   if (r >= nreads) return;
   const uint32_t qcut = ((uint32_t)r & pmask) ? qcut2 : qcut1;
   const uint8_t *seq = bases + off[r];
-  const uint8_t *qual = (quals && qcut > 0) ? quals + off[r] : nullptr;
+  const uint8_t *qual = quals ? quals + off[r] : nullptr;  // (uploaded only when they matter: quals_matter)
   const uint64_t len = off[r + 1] - off[r];
   const uint64_t cs = qh_contig_start(seq, len, qual, 0, (uint64_t)k, qcut, hcut);
   uint64_t node = kNoNode;
@@ -1364,7 +1364,7 @@ __global__ void k_reads_must_exist(TableView t, const uint8_t *bases, const uint
   const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= nreads) return;
   const uint8_t *seq = bases + off[r];
-  const uint8_t *qual = (quals && qcut > 0) ? quals + off[r] : nullptr;
+  const uint8_t *qual = quals ? quals + off[r] : nullptr;  // (uploaded only when they matter: quals_matter)
   const uint64_t len = off[r + 1] - off[r];
   unsigned long long n_kmers = 0, n_contigs = 0, n_absent = 0;
   uint32_t dummy_novel = 0, full = 0;

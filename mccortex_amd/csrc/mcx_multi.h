@@ -780,6 +780,7 @@ static int grp_add_reads_must_exist(mcx_group *G, int colour, const uint8_t *bas
     (void)hipFree(d_tmp);
   });
   const unsigned blocks = (unsigned)((nreads + 127) / 128);
+  const bool use_q = quals_matter(quals, off, nreads, fq, fq);
   auto launch = [&](int i, uint32_t phase) {
     mcx_graph *g = G->part[i];
     if (g->W == 1)
@@ -795,7 +796,7 @@ static int grp_add_reads_must_exist(mcx_group *G, int colour, const uint8_t *bas
     HIP_TRY(hipMalloc((void **)&d_bases[i], nb + 16));
     HIP_TRY(hipMalloc((void **)&d_off[i], (nreads + 1) * 8));
     HIP_TRY(hipMalloc((void **)&d_present[i], nb + 16));
-    if (quals && fq > 0) HIP_TRY(hipMalloc((void **)&d_quals[i], nb + 16));
+    if (use_q) HIP_TRY(hipMalloc((void **)&d_quals[i], nb + 16));
     HIP_TRY(hipMemcpyAsync(d_bases[i], bases + base0, nb, hipMemcpyHostToDevice, g->stream));
     if (d_quals[i]) HIP_TRY(hipMemcpyAsync(d_quals[i], quals + base0, nb, hipMemcpyHostToDevice, g->stream));
     HIP_TRY(hipMemcpyAsync(d_off[i], rel.data(), (nreads + 1) * 8, hipMemcpyHostToDevice, g->stream));

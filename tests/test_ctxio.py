@@ -250,6 +250,10 @@ def _random_records(rng, k, file_ncols, n, W):
     (31, 3, 2, [(0, 1), (2, 1), (1, 0)]),
     (63, 2, 3, [(1, 0), (1, 2)]),
     (45, 4, 2, [(3, 1)]),
+    (33, 2, 2, [(1, 0), (0, 1)]),               # filters, several file colours and must_exist at every key width
+    (65, 3, 2, [(0, 1), (2, 1), (1, 0)]),
+    (95, 2, 3, [(1, 0), (1, 2)]),
+    (127, 4, 2, [(3, 1)]),
 ])
 def test_add_records_matches_oracle(mcx, orc, k, file_ncols, ncols, filt):
     rng = np.random.default_rng(k * 10 + file_ncols)

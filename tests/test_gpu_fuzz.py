@@ -30,7 +30,7 @@ def _gpu_stream(mcx, k, stream_bytes, defer, ncap=1 << 20):
     return g
 
 
-@pytest.mark.parametrize("k", list(range(3, 64, 2)))
+@pytest.mark.parametrize("k", list(range(3, 128, 2)))
 def test_every_odd_k(mcx, orc, k):
     rng = np.random.default_rng(k)
     s = bytes(rng.choice(np.frombuffer(b"ACGTACGTACGTacgtN\n", np.uint8), 6000))

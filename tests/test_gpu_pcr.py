@@ -140,11 +140,10 @@ def test_argument_errors(mcx, orc):
     g.close()
 
 
-@pytest.mark.parametrize("seed", range(int(os.environ.get("MCX_FUZZ_SEEDS_BYTES", "6"))))
-def test_fuzz_arbitrary_bytes_lengths_and_cutoffs(mcx, orc, seed):
+def _fuzz_bytes_lengths_and_cutoffs(mcx, orc, seed, ks):
     """reads of arbitrary bytes and lengths (0 .. 3 k), arbitrary qualities, random preferences, in several batches"""
-    rng = np.random.default_rng(300 + seed)
-    k = int(rng.choice([5, 21, 31, 33, 63]))
+    rng = np.random.default_rng(seed)
+    k = int(rng.choice(ks))
     alphabet = np.concatenate([np.frombuffer(b"ACGT" * 30 + b"acgtNn-*", np.uint8), rng.integers(0, 256, 8).astype(np.uint8)])
     n = 2 * int(rng.integers(300, 1500))
     starts = [bytes(rng.choice(alphabet[:120], k + 3)) for _ in range(40)]     # few distinct read starts -> duplicates
@@ -176,3 +175,8 @@ def test_fuzz_arbitrary_bytes_lengths_and_cutoffs(mcx, orc, seed):
     assert {f: getattr(st, f) for f in FIELDS} == {f: getattr(ot, f) for f in FIELDS}
     _same_graph(mcx, g, og, k, 1)
     g.close()
+
+
+@pytest.mark.parametrize("seed", range(int(os.environ.get("MCX_FUZZ_SEEDS_BYTES", "6"))))
+def test_fuzz_arbitrary_bytes_lengths_and_cutoffs(mcx, orc, seed):
+    _fuzz_bytes_lengths_and_cutoffs(mcx, orc, 300 + seed, [5, 21, 31, 33, 63])
