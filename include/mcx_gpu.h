@@ -243,7 +243,12 @@ int mcx_graph_add_packed_dev(mcx_graph *g, int colour, const void *d_code, const
 int mcx_graph_partition_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes,
                                    int nparts, uint64_t bin_capacity,
                                    void *d_keys, void *d_edges, void *d_counts);
-/* Step 2 on the owner, after the exchange: insert n tuples. */
+/* Step 2 on the owner, after the exchange: insert n tuples -- for each, coverage[key][colour] += 1 and
+ * edges[key][colour] |= edge byte.  The keys are taken as given (W words each, most significant first): nothing is
+ * canonicalised -- a key and its reverse complement are two keys -- and the bits above 2k are not checked (they must
+ * be zero for a key that a read could yield; the small integers of `hashtest` are stored as they are).  k <= 63 with
+ * the deferred path on: split into pieces of one set of region bins each; otherwise one direct-insert launch.  On a
+ * shard of a split table the keys of other shards are inserted too (mcx_insert_stats::foreign_inserts counts them). */
 int mcx_graph_insert_tuples_dev(mcx_graph *g, int colour, const void *d_keys,
                                 const void *d_edges, uint64_t n);
 /* Owner of a canonical key in the exchange above (host-side helper for tests). */
@@ -252,7 +257,8 @@ uint32_t mcx_key_owner(const uint64_t *key_words, int kmer_size, int nparts);
 /* `mccortex<K> hashtest` (src/commands/ctx_exp_hashtest.c:40-69: `bkmer.b[0] = i; hash_table_find_or_insert(...)`):
  * find-or-insert of the n BinaryKmers whose most significant word is i, i in [first, first + n), all other words 0 --
  * generated on the device, no edges, colour 0.  Ends with the table drained (mcx_graph_sync); MCX_ERR_FULL when the
- * table cannot hold them. */
+ * table cannot hold them.  The keys go through mcx_graph_insert_tuples_dev as they are: not canonicalised, and where
+ * the integers pass the key bits of the top word (k = 33, 65: two bits) they are stored whole, as the reference does. */
 int mcx_graph_hashtest(mcx_graph *g, uint64_t first, uint64_t n);
 /* The command's -F mode (hash function only, nothing stored): the reference splits [0, n) into `nparts` ranges
  * (one per thread: range i starts at i * (n / nparts), the last one ends at n), XORs binary_kmer_hash(bkmer, 0) =
@@ -266,7 +272,12 @@ int mcx_debug_probe(void *d_buf, uint64_t cap_words, uint32_t nregions, uint32_t
 /* Like mcx_graph_insert_tuples_dev for tuples that sit in `nseg` segments of `seg_cap` slots with
  * the fills in device memory (d_counts[nseg], u64; a fill above seg_cap is read as seg_cap), so the
  * caller needs no host round trip to learn how many arrived: the overflow bins of the sharded
- * exchange are consumed this way. */
+ * exchange are consumed this way.  Keys as given, as above: not canonicalised, bits above 2k not checked.
+ * The whole call goes into ONE set of region bins, booked as min(nseg * seg_cap, tuples per set): when the fills
+ * exceed that, the tuples that find their (region, replica) segment full take the direct insert into the table
+ * (mcx_insert_stats::fallback_inserts) -- the graph is the same, the call slower.
+ * Needs the deferred path (k <= 63, a table of at least 64 sub-tables, "defer" not 0): otherwise MCX_ERR_ARG, before
+ * anything is allocated.  nseg == 0 or seg_cap == 0: MCX_OK, nothing happens. */
 int mcx_graph_insert_tuple_segments_dev(mcx_graph *g, int colour, const void *d_keys, const void *d_edges,
                                         const void *d_counts, uint32_t nseg, uint64_t seg_cap);
 

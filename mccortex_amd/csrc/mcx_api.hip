@@ -1752,7 +1752,7 @@ extern "C" int mcx_graph_insert_tuple_segments_dev(mcx_graph *g, int colour, con
   if (!nseg || !seg_cap) return MCX_OK;
   if (!d_keys || !d_edges || !d_counts) return fail(MCX_ERR_ARG, "null tuple buffers");
   HIP_TRY(hipSetDevice(g->device));
-  int rc = ensure_defer(g);
+  int rc = g->defer ? ensure_defer(g) : MCX_OK;  // (a refusal allocates nothing; ensure_defer switches the path off for a small table)
   if (rc != MCX_OK) return rc;
   if (!g->defer) return fail(MCX_ERR_ARG, "tuple segments need the deferred insert path (table too small or defer=0)");
   const uint64_t ub = std::min<uint64_t>((uint64_t)nseg * seg_cap, g->set_cap);  // the fills are only known on the device

@@ -97,6 +97,9 @@ def test_hashtest_command(built, orc):
     assert "using 1 thread (single-threaded code)" in err and "Output hash: 0" in err
     rc, _, err = run(63, "hashtest", "-k", "63", "-n", "1M", "-t", "4", str(n))
     assert rc == 0 and "filled: 200,000 / 1,081,344" in err and "using 4 threads (multi-threaded code)" in err, err
+    for maxk in (95, 127):  # three- and four-word keys: the direct insert (which keys: tests/test_gpu_tuples.py)
+        rc, _, err = run(maxk, "hashtest", "-k", str(maxk), "-n", "1M", str(n))
+        assert rc == 0 and "filled: 0 / 1,081,344 (0.00%)" in err and "filled: 200,000 / 1,081,344 (18.50%)" in err, err
     # more keys than the table holds: the reference's message
     rc, _, err = run(31, "hashtest", "-k", "31", "-n", "64K", str(n))
     assert rc == 1 and "Hash table is full" in err, err
