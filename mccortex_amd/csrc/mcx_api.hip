@@ -224,6 +224,7 @@ struct mcx_graph {
   uint32_t nsub = 0;            // sub-tables
   uint32_t b1 = 0, subs_per_bin = 0;
   uint64_t cap1 = 0, cap2 = 0;  // tuples per L1 (replica, bin) segment / per L2 (sub-table) bin
+  bool l2_idx32 = false;        // a sub-table bin spans less than 4 GiB: the LDS insert indexes its tuples with 32 bits
   // Replicas of every L1 bin.  A block appends to replica blockIdx % rep1; all blocks of a replica reserve from the same 64
   // counter lines once per tile.  8 (one per XCD) until round 6; for a one-colour graph with a large flush window 32 or 64
   // since (segments of >= 64 K tuples): k_stream_bin 23.3 -> 21.2 (32) -> 20.4 ms (64) per 6 G occurrences at C2.  The split
@@ -872,16 +873,25 @@ static uint64_t *l2_ptr(const mcx_graph *g, uint64_t off)
   return g->l2_keys + off * g->cap2 * g->W;
 }
 
-template <int W, bool ONECOL> static void launch_lds_insert_t(mcx_graph *g, int colour, uint32_t sub0, uint32_t nsub)
+template <int W, bool ONECOL, bool IDX32> static void launch_lds_insert_k(mcx_graph *g, int colour, uint32_t sub0, uint32_t nsub)
 {
   const size_t lds = Sub<W>::kSlots * (W + 1) * 8 + LdsQueue<W>::kTuples * 8 * W;
   static bool once_dev[64] = {false};  // per device: the attribute belongs to the function on one device
   bool &once = once_dev[g->device & 63];
-  if (!once) { allow_lds(k_lds_insert<W, ONECOL>, lds); once = true; }
+  if (!once) { allow_lds(k_lds_insert<W, ONECOL, IDX32>, lds); once = true; }
   BinOut bins{l2_ptr(g, g->l2_off), nullptr, g->l2_cnt + g->l2_off, g->cap2, nullptr, nullptr, nullptr, 0};
   SpanGuard sp(g, "k_lds_insert");
-  hipLaunchKernelGGL((k_lds_insert<W, ONECOL>), dim3((unsigned)std::min<uint64_t>(nsub, (uint64_t)(g->grid_insert ? g->grid_insert : g->grid * 4))),
+  hipLaunchKernelGGL((k_lds_insert<W, ONECOL, IDX32>), dim3((unsigned)std::min<uint64_t>(nsub, (uint64_t)(g->grid_insert ? g->grid_insert : g->grid * 4))),
                      dim3(LdsCfg<W>::kThreads), lds, g->stream, g->t, (uint32_t)colour, bins, sub0, nsub, g->d_ctr);
+}
+
+// (32-bit tuple indices exist for the one-word, one-colour insert only: mcx_defer.h, k_lds_insert)
+template <int W, bool ONECOL> static void launch_lds_insert_t(mcx_graph *g, int colour, uint32_t sub0, uint32_t nsub)
+{
+  if constexpr (W == 1 && ONECOL) {
+    if (g->l2_idx32) return launch_lds_insert_k<W, ONECOL, true>(g, colour, sub0, nsub);
+  }
+  launch_lds_insert_k<W, ONECOL, false>(g, colour, sub0, nsub);
 }
 
 template <int W, bool ONECOL>
@@ -1088,6 +1098,7 @@ static int ensure_defer(mcx_graph *g)
     g->cap2 = g->nsub == 1 ? tcap + 8192 : (uint64_t)((double)tcap / g->nsub * cap2_slack) + 1024;
     g->cap1 = (g->cap1 + 1) & ~1ull;  // even: every segment starts 16-byte aligned (vector loads)
     g->cap2 = (g->cap2 + 1) & ~1ull;
+    g->l2_idx32 = g->cap2 * 8 * g->W < (1ull << 32) - 8 * kLdsIdxSlack;  // (a thread's index runs up to kLdsIdxSlack tuples past the fill)
     if (g->cap1 >= 0xFFFFFFFFull || g->cap2 >= 0xFFFFFFFFull) continue;
     const uint64_t n1 = (uint64_t)g->nsets * g->b1 * g->rep1 * g->cap1;
     const bool ok = hipMalloc((void **)&g->l1_keys, n1 * 8 * g->W) == hipSuccess &&

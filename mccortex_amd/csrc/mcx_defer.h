@@ -139,8 +139,10 @@ template <int W, int NB, bool FULL, class G = Geo256> struct BinLds {
 // addresses, masks) is then recomputed per tile in an instruction or two -- hoisted out of the
 // loop these values were spilled to scratch, and a scratch reload waits for the next tile's
 // prefetch (vmcnt counts in order).
-// Used by k_stream_bin's tile loop only (the write-out loop of bin_writeout keeps threadIdx.x: see the
-// note there and profiles/r03_writeout_fault.md).
+// Used by k_stream_bin's tile loop and by the one-word LDS insert (k_lds_insert: the slice copies' offsets and the
+// batch indices of run_lean, which only add constants to it and clamp against the fill).  The write-out loop of
+// bin_writeout keeps threadIdx.x: a loop INDEX started from this value met a miscompiled guarded difference there
+// (see the note there and profiles/r03_writeout_fault.md); neither user above starts a loop index from it.
 __device__ __forceinline__ uint32_t tid_now()
 {
   uint32_t t = threadIdx.x;
@@ -1181,17 +1183,30 @@ __device__ __forceinline__ void slice_store(const TableView &t, uint32_t sub, ui
   }
 }
 
-template <int W, bool ONECOL>
+// The batch loop of the insert may run its tuple index up to this many tuples past a bin's fill (four batches of the
+// widest workgroup); the host allows 32-bit indices only where that still fits (mcx_api.hip, l2_idx32).
+constexpr uint64_t kLdsIdxSlack = 4ull * 512 * 4;
+
+// IDX32 (one-word keys, one colour): a bin spans less than 4 GiB, so tuples are indexed with 32 bits.
+template <int W, bool ONECOL, bool IDX32 = false>
 __global__ __launch_bounds__(LdsCfg<W>::kThreads, LdsCfg<W>::kMinWaves) void k_lds_insert(TableView t, uint32_t col, BinOut bins,
                                                                        uint32_t sub0, uint32_t nsub, Counters *ctr)
 {
   constexpr int kLdsThreads = LdsCfg<W>::kThreads;
   constexpr int kLdsBatch = LdsCfg<W>::kBatch;
+  // The one-word, one-colour insert has a batch loop of its own (run_lean below); every other instantiation keeps lds_try.
+  constexpr bool kLean = W == 1 && ONECOL;
+  static_assert(!IDX32 || kLean, "32-bit tuple indices: one-word, one-colour insert only");
+  static_assert(4ull * kLdsThreads * kLdsBatch <= kLdsIdxSlack, "index slack");
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
   unsigned long long *lds = reinterpret_cast<unsigned long long *>(dyn_lds);
   const int tid = threadIdx.x;
   uint32_t n_novel = 0, full = 0;
-  // occurrences that lds_try could not finish (packed tuples, as they came): behind the slice
+  // kLean: the thread index as tid_now(), so that what the slice copies derive from it (LDS and HBM offsets, 30 registers)
+  // is recomputed per visit and not kept (and spilled) across the batch loop
+  auto tid_v = [&]() -> int { if constexpr (kLean) return (int)tid_now(); else return tid; };
+  // occurrences that the straight-line probe (lds_try, or probe of run_lean) could not finish (packed tuples, as
+  // they came): behind the slice
   unsigned long long *queue = lds + Sub<W>::kSlots * (W + 1);
   constexpr uint32_t kQueueCap = LdsQueue<W>::kTuples;
   __shared__ uint32_t s_nq;
@@ -1242,7 +1257,7 @@ __global__ __launch_bounds__(LdsCfg<W>::kThreads, LdsCfg<W>::kMinWaves) void k_l
     MCX_PH(0)
     if (tid == 0) bins.counts[bi] = 0;
     if (!kPrefetch) slice_fetch<W, ONECOL, kLdsThreads>(t, sub, col, tid, v, zeros_known);
-    slice_to_lds<W, ONECOL, kLdsThreads>(lds, tid, v);
+    slice_to_lds<W, ONECOL, kLdsThreads>(lds, tid_v(), v);
     __syncthreads();
     MCX_PH(1)
 
@@ -1292,7 +1307,124 @@ __global__ __launch_bounds__(LdsCfg<W>::kThreads, LdsCfg<W>::kMinWaves) void k_l
         load_batch(j0 + 3 * kStep, tb);
       }
     };
-    if (kPrefetch && nb < nsub) run(std::true_type{}); else run(std::false_type{});
+    // One-word keys, one colour: the protocol of lds_try with less work on the path that every lane takes.  want's
+    // halves are built with 32-bit shifts (lbq is uniform), the hit slot's address comes from the four compare masks
+    // and not from a chain of selects, the empty-slot search runs only for lanes without a hit, and with IDX32 the
+    // index compare and the tuple loads are 32-bit (scalar base + 32-bit offset).
+    // (Probing one tuple AHEAD -- bucket of tuple q + 1 read before tuple q is applied, so that its reads travel with
+    // the atomic of q -- was built and measured in round 7: 16.15 ms per 10 steps at C2 against 15.55 for this loop,
+    // three alternating runs each within 0.02 ms.  The kernel has other waves to cover an LDS round trip; the probe
+    // in flight only costs registers and LDS queue depth.  DESIGN.md section 5, round 7.)
+    auto run_lean = [&](auto has_next) {
+      typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+      typedef MCX_LDS_AS unsigned long long lds_u64;
+      typedef MCX_LDS_AS unsigned char lds_u8;
+      using idx_t = std::conditional_t<IDX32, uint32_t, uint64_t>;
+      lds_u8 *const l3 = (lds_u8 *)lds;
+      const uint32_t lbq = lbq_of(t), s31 = 31u - lbq, sb = 22u - lbq;
+      const uint32_t g0 = (t.part << t.lb1) | region;
+      const idx_t nn = (idx_t)n;
+      const uint64_t *kin = bins.keys + (uint64_t)bi * bins.cap;
+      constexpr idx_t kSt = (idx_t)kStep;
+      // (jt = j0 + the thread's index, taken from tid_now(): derived from a loop-invariant thread index, the four
+      // indices of a batch and their byte offsets were hoisted out of the loop, and spilled)
+      auto loadb = [&](idx_t jt, uint64_t (&tk)[kLdsBatch]) {
+#pragma unroll
+        for (int q = 0; q < kLdsBatch; q++) {
+          idx_t i = jt + (idx_t)(q * kLdsThreads);
+          i = i < nn ? i : 0;
+          if constexpr (IDX32) tk[q] = *reinterpret_cast<const uint64_t *>(reinterpret_cast<const unsigned char *>(kin) + (i << 3));
+          else tk[q] = kin[i];
+        }
+      };
+      // One straight-line probe of the start bucket, as lds_try.  Returns true where the tuple found the set-aside queue
+      // full and has to take lds_apply before its batch is reloaded (drain).
+      auto probe = [&](uint64_t tp, bool valid) -> bool {
+        const uint32_t tlo = (uint32_t)tp, qhi = (uint32_t)(tp >> 32) & (uint32_t)(kQMask >> 32);
+        const uint32_t m = (tlo ^ qhi) * 0x9E3779B1u;  // region_mix
+        // key = quotient << lbq | remainder, remainder = (owner, region) ^ mix_g(m): x >> (32 - lbq) as (x >> 1) >> (31 - lbq), lbq may be 0
+        const uint32_t wlo = (tlo << lbq) | (((m >> 1) >> s31) ^ g0);
+        const uint32_t whi = (qhi << lbq) | ((tlo >> 1) >> s31) | (uint32_t)(kFlag >> 32);
+        const uint32_t bucket = (m >> sb) & (Sub<W>::kBuckets - 1u);  // mix_bucket
+        // byte offset of slot 0's key in the image (the half swap of lds_phys1); slot 2's: a0 ^ 16
+        const uint32_t a0 = bucket * (kBucket * 8u) + ((bucket >> 3) & 1u) * 16u;
+        const u64x2 lo = *(const MCX_LDS_AS u64x2 *)(l3 + a0);          // keys of logical slots 0-1
+        const u64x2 hi = *(const MCX_LDS_AS u64x2 *)(l3 + (a0 ^ 16u));  // ... and 2-3
+        const unsigned long long want = ((unsigned long long)whi << 32) | wlo;
+        const bool h0 = lo.x == want, h1 = lo.y == want, h2 = hi.x == want, h3 = hi.y == want;
+        const bool hit = valid & (h0 | h1 | h2 | h3);
+        const uint32_t e = (uint32_t)(tp >> 56);
+        if (hit) {  // (a key sits in one slot only: at most one of the four is set)
+          const uint32_t a = (a0 ^ ((h2 | h3) ? 16u : 0u)) | ((h1 | h3) ? 8u : 0u);
+          lds_u64 *val = (lds_u64 *)(l3 + a) + kLdsVal1;
+          const unsigned long long old = __hip_atomic_fetch_add(val, 256ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          if (e & ~(uint32_t)old) __hip_atomic_fetch_or(val, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        if (valid & !hit) {
+          const bool e0 = lo.x == 0, e1 = lo.y == 0, e2 = hi.x == 0, e3 = hi.y == 0;
+          bool done = false;
+          if (e0 | e1 | e2 | e3) {  // the first empty slot in probe order
+            const uint32_t a = (a0 ^ ((e0 | e1) ? 0u : 16u)) | ((e0 | (!e1 & e2)) ? 0u : 8u);
+            lds_u64 *kp = (lds_u64 *)(l3 + a);
+            unsigned long long seen = 0;
+            done = __hip_atomic_compare_exchange_strong(kp, &seen, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            // Coverage and edges follow in this block, as "+ 0" and "| 0" where the slot went to another lane.  In a
+            // block of their own the slot's address was live from one divergent block into a later one, and such a
+            // register stays allocated round the whole batch loop: two per unrolled tuple.
+            n_novel += done ? 1u : 0u;
+            __hip_atomic_fetch_add(kp + kLdsVal1, done ? 256ULL : 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_or(kp + kLdsVal1, (unsigned long long)(done ? e : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
+          if (!done) {  // bucket full of other keys, or the slot went to another lane: set aside
+            const uint32_t qi = atomicAdd(&s_nq, 1u);
+            if (qi < kQueueCap) queue[qi] = tp;
+            else return true;
+          }
+        }
+        return false;
+      };
+      // The queue is full (rare): the tuples of a batch that met it (bits of `slow`) take the general loop once the
+      // batch is through, behind a branch that the whole wave takes: one copy of lds_apply and probe_insert per
+      // batch and not one per tuple.
+      auto drain = [&](uint32_t slow, const uint64_t (&tk)[kLdsBatch]) {
+        if (__builtin_amdgcn_ballot_w64(slow != 0)) {
+          while (slow) {
+            const uint32_t q = (uint32_t)__ffs(slow) - 1u;
+            slow &= slow - 1u;
+            Kmer<W> tq, key;
+            uint32_t bucket, e;
+            tq.w[0] = q == 0 ? tk[0] : q == 1 ? tk[1] : q == 2 ? tk[2] : tk[3];
+            unpack(tq, key, bucket, e);
+            apply_slow(key, bucket, e);
+          }
+        }
+      };
+      static_assert(kLdsBatch == 4, "drain selects among four tuples");
+      // batch jt0 .. applied, then reloaded for two batches on (as `run` above)
+      auto apply_reload = [&](idx_t jt, uint64_t (&tk)[kLdsBatch]) {
+        uint32_t slow = 0;
+#pragma unroll
+        for (int q = 0; q < kLdsBatch; q++)
+          if (probe(tk[q], jt + (idx_t)(q * kLdsThreads) < nn)) slow |= 1u << q;
+        drain(slow, tk);
+        loadb(jt + 2 * kSt, tk);
+      };
+      uint64_t ta[kLdsBatch], tb[kLdsBatch];
+      const idx_t jt0 = (idx_t)tid_now();
+      loadb(jt0, ta);
+      loadb(kSt + jt0, tb);
+      if (decltype(has_next)::value) slice_fetch<W, ONECOL, kLdsThreads>(t, sub0 + nb, col, tid_v(), v, zeros_known);
+      for (idx_t j0 = 0; j0 < nn; j0 += 2 * kSt) {
+        const idx_t jt = j0 + (idx_t)tid_now();
+        apply_reload(jt, ta);
+        apply_reload(jt + kSt, tb);
+      }
+    };
+    if constexpr (kLean) {
+      if (kPrefetch && nb < nsub) run_lean(std::true_type{}); else run_lean(std::false_type{});
+    } else {
+      if (kPrefetch && nb < nsub) run(std::true_type{}); else run(std::false_type{});
+    }
     MCX_PH(2)
     __syncthreads();
     MCX_PH(3)
@@ -1310,7 +1442,7 @@ __global__ __launch_bounds__(LdsCfg<W>::kThreads, LdsCfg<W>::kMinWaves) void k_l
       if (tid == 0) s_nq = 0;
     }
     MCX_PH(4)
-    slice_store<W, ONECOL, kLdsThreads>(t, sub, col, tid, lds);
+    slice_store<W, ONECOL, kLdsThreads>(t, sub, col, tid_v(), lds);
     if (tid == 0 && t.touch) atomicOr(&t.touch[1 + (sub >> 5)], 1u << (sub & 31u));
     bi = nb;
     MCX_PH(5)
