@@ -567,6 +567,59 @@ int mcx_sort_records(void *recs, uint64_t nrecs, int kmer_size, int ncols, int d
 int mcx_records_sorted(const void *recs, uint64_t nrecs, int kmer_size, int ncols, int device,
                        int64_t *first_unsorted);
 
+/* `join` (src/commands/ctx_join.c; graph_writer_merge_mkhdr of src/graph/graph_writer.c; graph_load of
+ * src/graph/graphs_load.c): merge .ctx files by a device sort and a segmented reduce -- no graph handle, no hash table,
+ * so there is no capacity to guess and nothing that can be full, and the output is always sorted by key.
+ *   mcx_join_create       out_ncols colours in the output; n_isec intersection graphs (`-i`, 0 = none).
+ *       MCX_JOIN_KEEP_EMPTY: a key of the intersection that no input graph supplies is written as an all-zero record
+ *       (graph_write_empty plus the update); without the flag it is not written.
+ *   mcx_join_configure    test knobs, the answers must not change with them: "grid" (at most n blocks per launch, 0 =
+ *       CUs x 8) and "out_chunk" (bytes of output per sink call, 0 = 64 MiB; a seam may fall inside a record).
+ * Three entries serve one caller each and are kept small on purpose: get_stats (the command's per-file "[GReader]
+ * Loaded" line), buffer (the command's pinned read buffer: a C host has no other way to pinned memory) and phases
+ * (tools/bench_join.py).
+ *   mcx_join_get_stats    the counts so far (the records read and kept; the rest is filled by finish)
+ *   mcx_join_phases       host-clock milliseconds so far of the four phases (tools/bench_join.py): upload + key
+ *       extraction (the add_records calls), sort, runs + intersection, reduce + write-out (the sink's time included)
+ *   mcx_join_buffer       pinned host memory of `bytes` bytes owned by the handle (one at a time; freed by the next call
+ *       and by destroy): a reader fills it from the file and hands it to mcx_join_add_records.
+ *   mcx_join_add_records  host records in .ctx body layout (W x u64 key, file_ncols x u32 coverage, file_ncols x u8
+ *       edges, byte-packed), any number of calls per file.  source = -1: an input graph, whose file colour from_col[i]
+ *       goes to output colour into_col[i] (pairs may repeat sources and targets); source = 0 .. n_isec - 1: the
+ *       intersection graph of that rank, every selected colour flattened into one (into_col is not read); rank 0
+ *       supplies the edge mask.  A record whose coverage is zero in all the colours the filter selects is dropped here
+ *       (keep_kmer, graphs_load.c:121-124), edges or not.  The records stay in HBM as uploaded, with one 64-bit locator
+ *       per kept record: the cost is that of the input bytes, not records x out_ncols.  Synchronous.
+ *   mcx_join_finish       sorts the locators by key (all W words), reduces every run of equal keys to one record and
+ *       hands the records to `sink` in ascending key order, in consecutive byte ranges of at most "out_chunk" bytes.
+ *       covg[into] is the sum, saturating at 2^32 - 1 (SAFE_ADD_COVG), and edges[into] the OR over every (record of the
+ *       run, filter pair of its call); colours nobody loads stay zero.  A key that a file repeats, or a file given
+ *       twice, is summed like any other.  With intersection graphs (ctx_join.c:262-306 as it behaves with --ncols 1):
+ *       a key is kept iff it survives the drop rule in EVERY intersection source -- presence per source, where the
+ *       reference counts loaded records, which differs only for a file that repeats a key; records of other keys are
+ *       dropped; every output colour's edges are ANDed with the OR, over the selected colours, of the edges that
+ *       source 0 has for the key.  The handle is spent afterwards (a second finish writes nothing).
+ *       MCX_ERR_NOMEM (from add_records or finish) when the records, the sort scratch or the output chunk do not fit
+ *       the free HBM: splitting the key range into several passes is out of scope. */
+typedef struct mcx_join mcx_join;
+enum { MCX_JOIN_KEEP_EMPTY = 1 };
+typedef struct {
+  uint64_t recs_read, recs_kept;            /* input graphs */
+  uint64_t isec_recs_read, isec_recs_kept;  /* intersection graphs */
+  uint64_t kmers_written;
+  uint64_t kmers_intersection;              /* keys present in every intersection source (0 without any) */
+  uint64_t kmers_written_no_covg;           /* all-zero records written under MCX_JOIN_KEEP_EMPTY */
+} mcx_join_stats;
+int mcx_join_create(mcx_join **j, int kmer_size, int out_ncols, int n_isec, uint32_t flags, int device);
+int mcx_join_configure(mcx_join *j, const char *key, uint64_t value);
+int mcx_join_get_stats(const mcx_join *j, mcx_join_stats *stats);
+int mcx_join_phases(const mcx_join *j, double *ms /* [4] */);
+int mcx_join_buffer(mcx_join *j, size_t bytes, void **ptr);
+int mcx_join_add_records(mcx_join *j, int source, const void *recs, uint64_t nrecs, int file_ncols,
+                         const int32_t *from_col, const int32_t *into_col, int nmap);
+int mcx_join_finish(mcx_join *j, mcx_sink_fn sink, void *ctx, mcx_join_stats *stats);
+void mcx_join_destroy(mcx_join *j);
+
 /* Sharded build, exchange format v3 ("reads travel, not occurrences"; odd k in 29..63,
  * mcx_superk_supported(); records are mcx_superk_record_bytes(k) = 16 bytes for one-word keys, 32
  * for two-word keys: an 80-base window).  The owner of a k-mer is a function of its canonical minimizer

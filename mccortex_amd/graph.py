@@ -26,6 +26,7 @@ SYMBOLS = [
     "mcx_graph_subgraph_begin", "mcx_graph_subgraph_seed_reads", "mcx_graph_subgraph_seed_stream_dev", "mcx_graph_subgraph_finish",
     "mcx_graph_reads_touch", "mcx_graph_reads_touch_stream_dev",
     "mcx_graph_coverage", "mcx_graph_coverage_stream_dev", "mcx_graph_coverage_text",
+    "mcx_join_create", "mcx_join_configure", "mcx_join_get_stats", "mcx_join_phases", "mcx_join_buffer", "mcx_join_add_records", "mcx_join_finish", "mcx_join_destroy",
 ]
 
 
@@ -110,6 +111,14 @@ class UnitigsStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class JoinStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("recs_read", "recs_kept", "isec_recs_read", "isec_recs_kept", "kmers_written",
+                                          "kmers_intersection", "kmers_written_no_covg")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class UnitigsArrays(C.Structure):
     """mcx_unitigs_arrays (device pointers)"""
     _fields_ = [(n, C.c_void_p) for n in ("keys", "unitig", "rank", "orient", "first", "length")]
@@ -160,6 +169,15 @@ def lib():
     L.mcx_sort_records.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_int]
     L.mcx_records_sorted.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
     L.mcx_graph_intersect_finish.argtypes = [vp, u64p]
+    L.mcx_join_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]
+    L.mcx_join_configure.argtypes = [vp, C.c_char_p, C.c_uint64]
+    L.mcx_join_add_records.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_int, vp, vp, C.c_int]
+    L.mcx_join_finish.argtypes = [vp, SINK_FN, vp, C.POINTER(JoinStats)]
+    L.mcx_join_get_stats.argtypes = [vp, C.POINTER(JoinStats)]
+    L.mcx_join_buffer.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
+    L.mcx_join_phases.argtypes = [vp, C.POINTER(C.c_double)]
+    L.mcx_join_destroy.argtypes = [vp]
+    L.mcx_join_destroy.restype = None
     L.mcx_graph_unitig_stats.argtypes = [vp, vp]
     L.mcx_graph_clean.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(CleanStats), vp]
     L.mcx_graph_pop_bubbles.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PopStats)]
@@ -677,6 +695,60 @@ def sort_records(recs, kmer_size, ncols, device=0):
     assert a.size % rs == 0
     _check(lib().mcx_sort_records(_ptr(a), a.size // rs, kmer_size, ncols, device))
     return a.tobytes()
+
+
+JOIN_KEEP_EMPTY = 1
+
+
+class Join:
+    """`join` on the device: .ctx records of several files merged by a sort and a segmented reduce (no table)."""
+
+    def __init__(self, kmer_size, out_ncols, n_isec=0, keep_empty=False, device=0):
+        self.L = lib()
+        self.h = None
+        self.k, self.W, self.ncols = kmer_size, _words(kmer_size), out_ncols
+        h = C.c_void_p()
+        _check(self.L.mcx_join_create(C.byref(h), kmer_size, out_ncols, n_isec, JOIN_KEEP_EMPTY if keep_empty else 0, device))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.L.mcx_join_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def configure(self, key, value):
+        _check(self.L.mcx_join_configure(self.h, key.encode(), int(value)))
+
+    def add(self, recs, file_ncols, colour_filter, source=-1):
+        """recs: .ctx body bytes of a file with file_ncols colours; colour_filter: [(from, into)]; source -1 = an
+        input graph, r >= 0 = the intersection graph of rank r (only the `from` side of its filter counts)"""
+        recs = np.frombuffer(recs, dtype=np.uint8) if isinstance(recs, (bytes, bytearray, memoryview)) else np.ascontiguousarray(recs, dtype=np.uint8)
+        rs = 8 * self.W + 5 * file_ncols
+        assert recs.size % rs == 0
+        frm = np.array([f for f, _ in colour_filter], dtype=np.int32)
+        into = np.array([t for _, t in colour_filter], dtype=np.int32)
+        _check(self.L.mcx_join_add_records(self.h, source, _ptr(recs), recs.size // rs, file_ncols, _ptr(frm), _ptr(into), len(frm)))
+
+    def phases(self):
+        """host-clock ms so far: upload + key extraction, sort, runs + intersection, reduce + write-out"""
+        ms = (C.c_double * 4)()
+        _check(self.L.mcx_join_phases(self.h, ms))
+        return dict(zip(("upload_extract_ms", "sort_ms", "runs_isec_ms", "reduce_write_ms"), [float(x) for x in ms]))
+
+    def finish(self, keep=True):
+        """-> (body bytes in ascending key order, stats dict); keep=False drops the bytes (benchmarks)"""
+        parts = []
+
+        def sink(_ctx, ptr, n):
+            parts.append(C.string_at(ptr, n) if keep else n)
+            return 0
+
+        st = JoinStats()
+        _check(self.L.mcx_join_finish(self.h, SINK_FN(sink), None, C.byref(st)))
+        self.chunks = [len(p) if keep else p for p in parts]
+        return (b"".join(parts) if keep else b""), st.as_dict()
 
 
 def records_sorted(recs, kmer_size, ncols, device=0):

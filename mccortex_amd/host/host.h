@@ -198,6 +198,7 @@ int ctx_subgraph(int argc, char **argv);    /* src/commands/ctx_subgraph.c */
 int ctx_unitigs(int argc, char **argv);     /* src/commands/ctx_unitigs.c */
 int ctx_reads(int argc, char **argv);       /* src/commands/ctx_reads.c */
 int ctx_coverage(int argc, char **argv);    /* src/commands/ctx_coverage.c */
+int ctx_join(int argc, char **argv);        /* src/commands/ctx_join.c */
 int ctx_hashtest(int argc, char **argv);    /* src/commands/ctx_exp_hashtest.c */
 
 /* ---- sequence output of `reads` (src/basic/seqout.{h,c}): <O>.fq.gz / .fa.gz / .txt.gz, for a paired task also
