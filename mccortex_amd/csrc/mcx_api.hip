@@ -35,6 +35,7 @@
 #include "mcx_subgraph.h"
 #include "mcx_reads.h"
 #include "mcx_coverage.h"
+#include "mcx_chunk.h"
 
 using namespace mcx;
 
@@ -175,7 +176,6 @@ class StagePool {
   int T_ = 0, next_ = 0, pending_ = 0;
 };
 
-constexpr uint64_t kCarry = 128;  // context bytes carried between chunks
 constexpr uint32_t kL1Sets = 32;  // L1 bin sets of a graph with several colours (mcx_graph::nsets; <= TupleIn::set_map)
 // New stream bytes per staged chunk (MCX_STAGE_BYTES overrides, for tests of the chunk seams).
 static uint64_t stage_bytes()
@@ -306,7 +306,7 @@ struct mcx_graph {
   unsigned long long *d_rt_cnt = nullptr;  // [k-mer occurrences probed, occurrences found] of the current host call
   uint64_t *d_rt_mask = nullptr;           // hit masks of the device entry, 1 bit per stream position (grows, never shrinks)
   uint64_t rt_mask_bytes = 0;
-  uint64_t reads_chunk = 0;                // test knob: stream bytes per chunk of mcx_graph_reads_touch (0 = what a staging buffer holds)
+  uint64_t reads_chunk = 0;                // test knob: stream bytes per chunk of mcx_graph_reads_touch and of coverage_batch (0 = what a staging buffer holds)
 };
 
 // how the kernels that walk records / reads on every shard tell their own keys (mcx_kernels.h: OwnerSpec)
@@ -2364,6 +2364,37 @@ static int ensure_stage(mcx_graph *g)
   return MCX_OK;
 }
 
+// the staging pair whose turn it is, once the device has finished with its previous chunk (ev[b])
+static int next_stage(mcx_graph *g, int *b)
+{
+  *b = g->cur;
+  g->cur = (g->cur + 1) % mcx_graph::kStageBufs;
+  HIP_TRY(hipEventSynchronize(g->ev[*b]));
+  return MCX_OK;
+}
+
+// Text of `total` bytes on the device to a sink, `chunk` bytes at a time through the first two staging pairs:
+// produce(c0, b) sends text bytes [c0, c0 + chunk) on their way into h_stage[b] and records ev_copy[b] behind them;
+// chunk i + 1 is produced while chunk i is with the sink, and a buffer is produced into again only after the sink has
+// returned from it.  Nothing is in flight on the staging buffers when this returns, whatever it returns.
+template <class Produce>
+static int drain_to_sink(mcx_graph *g, uint64_t total, uint64_t chunk, Produce produce, mcx_sink_fn sink, void *ctx, const char *sink_failed)
+{
+  auto run = [&]() -> int {
+    int rc = total ? produce((uint64_t)0, 0) : MCX_OK, b = 0;
+    for (uint64_t c0 = 0; c0 < total && rc == MCX_OK; c0 += chunk, b ^= 1) {
+      if (c0 + chunk < total && (rc = produce(c0 + chunk, b ^ 1)) != MCX_OK) break;
+      HIP_TRY(hipEventSynchronize(g->ev_copy[b]));
+      if (sink(ctx, g->h_stage[b], (size_t)(std::min(total, c0 + chunk) - c0)) != 0) rc = fail(MCX_ERR_SINK, "%s", sink_failed);
+    }
+    return rc;
+  };
+  const int rc = run();
+  (void)hipStreamSynchronize(g->stream);
+  (void)hipStreamSynchronize(g->cstream);
+  return rc;
+}
+
 static int add_reads_qh(mcx_graph *g, int colour, const uint8_t *bases, const uint8_t *quals,
                         const uint64_t *off, uint64_t nreads, uint8_t fq, uint8_t hp);
 static int add_reads_must_exist(mcx_graph *g, int colour, const uint8_t *bases, const uint8_t *quals,
@@ -2652,28 +2683,22 @@ extern "C" int mcx_graph_add_reads(mcx_graph *g, int colour, const uint8_t *base
   }
 
   const uint64_t off_region = stage_off_region();  // byte offset of the staged offsets (8-aligned)
-  const uint64_t max_offs = kStageBytes / 16;
-  uint64_t r = 0, r_pos = 0;  // next read, bytes of it already staged
-  uint8_t carry[kCarry];
-  memset(carry, '\n', kCarry);
-  while (r < nreads) {
-    const int b = g->cur;
-    g->cur = (g->cur + 1) % mcx_graph::kStageBufs;
-    HIP_TRY(hipEventSynchronize(g->ev[b]));  // previous use of this buffer finished
+  const ChunkLayout lay{kCarry, kStageBytes, kStageBytes / 16, 0, false};  // the carry layout of mcx_chunk.h
+  ReadChunker ck(bases, off, nreads);
+  while (!ck.done()) {
+    int b;
+    if ((rc = next_stage(g, &b)) != MCX_OK) return rc;
     uint8_t *hs = g->h_stage[b];
     uint64_t *hoff = reinterpret_cast<uint64_t *>(hs + off_region);
-    memcpy(hs, carry, kCarry);
-    uint64_t L = 0, nwhole = 0;
-    const uint64_t r0 = r;
-    long long piece_of = -1;  // >= 0: chunk holds a piece of this (long) read only
-    if (r_pos == 0 && stage_threads() > 1) {
+    uint64_t nf = 0, bytes = 0;
+    if (ck.r_pos == 0 && stage_threads() > 1) {
       // Whole reads that fit this chunk, found without copying; then a few threads copy their
       // share (read r lands at (off[r] - off[r0]) + (r - r0): every read is followed by one
       // separator).  One thread moves ~10 GB/s into pinned memory, PCIe takes ~25 GB/s.
-      uint64_t nf = 0, bytes = 0;
-      while (r0 + nf < nreads && nf < max_offs) {
+      const uint64_t r0 = ck.r;
+      while (r0 + nf < nreads && nf < lay.max_reads) {
         const uint64_t len = off[r0 + nf + 1] - off[r0 + nf];
-        if (bytes + len + 1 > kStageBytes) break;
+        if (bytes + len + 1 > lay.cap) break;
         bytes += len + 1;
         nf++;
       }
@@ -2689,47 +2714,23 @@ extern "C" int mcx_graph_add_reads(mcx_graph *g, int colour, const uint8_t *base
           }
         };
         StagePool::get().run(T, work);
-        nwhole = nf; L = bytes; r += nf;
-      }
+        ck.r += nf;
+      } else nf = bytes = 0;
     }
-    while (r < nreads) {
-      const uint64_t len = off[r + 1] - off[r];
-      const uint64_t remain = len - r_pos;
-      if (r_pos == 0 && remain + 1 <= kStageBytes - L && nwhole < max_offs) {
-        hoff[nwhole++] = kCarry + L;
-        memcpy(hs + kCarry + L, bases + off[r], len);
-        L += len;
-        hs[kCarry + L++] = '\n';
-        r++;
-      } else if (L == 0) {  // read longer than a chunk (or its tail): stage a piece on its own
-        const uint64_t take = std::min(remain, kStageBytes - 1);
-        memcpy(hs + kCarry, bases + off[r] + r_pos, take);
-        L = take;
-        r_pos += take;
-        piece_of = (long long)r;
-        if (r_pos == len) { hs[kCarry + L++] = '\n'; r++; r_pos = 0; }
-        break;
-      } else {
-        break;
-      }
-    }
-    hoff[nwhole] = kCarry + L;
-    const uint64_t total = kCarry + L;
-    memcpy(carry, hs + total - kCarry, kCarry);
-    // pad the tail so the 16-byte chunk loads of the kernel stay inside the copy
-    memset(hs + total, '\n', 64);
+    const Chunk c = ck.fill(lay, hs, hoff, nf, bytes);  // (behind the reads the threads placed, if any)
+    const uint64_t nwhole = c.n, total = kCarry + c.L;
     { int rc_ = flush_if_device_idle(g); if (rc_ != MCX_OK) return rc_; }
-    HIP_TRY(hipMemcpyAsync(g->d_stage[b], hs, total + 64, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(g->d_stage[b], hs, total + kChunkPad, hipMemcpyHostToDevice, g->stream));  // (the pad: the kernel's 16-byte loads stay inside the copy)
     if (nwhole)
       HIP_TRY(hipMemcpyAsync(g->d_stage[b] + off_region, hoff, (nwhole + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, g->stream));
     StreamLaunch SL{g->d_stage[b], total, kCarry - (uint64_t)g->k, total - (uint64_t)g->k,
-                    piece_of >= 0 ? d_flags + piece_of : nullptr};
+                    c.piece_of >= 0 ? d_flags + c.piece_of : nullptr};  // (a chunk that holds a piece of a long read only)
     rc = submit_stream(g, SL, colour);
     if (rc != MCX_OK) return rc;
     if (nwhole) {
       hipLaunchKernelGGL(k_read_flags, dim3((unsigned)((nwhole + 255) / 256)), dim3(256), 0, g->stream,
                          (const uint8_t *)g->d_stage[b], (const uint64_t *)(g->d_stage[b] + off_region), nwhole,
-                         g->k, d_flags + r0);
+                         g->k, d_flags + c.r0);
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(g->ev[b], g->stream));
@@ -3128,6 +3129,17 @@ extern "C" int mcx_graph_add_records(mcx_graph *g, const void *recs, uint64_t nr
   return MCX_OK;
 }
 
+// The refusals of the commands that want one whole, plain table: `what` names the command in the messages, `why` is
+// the reason in brackets (with its leading blank) that it cannot take a graph split over devices, or ""
+static int whole_table_only(const mcx_graph *g, const char *what, const char *why)
+{
+  if (!g) return fail(MCX_ERR_ARG, "null graph");
+  if (g->as_group || g->group || g->t.lbo || g->own_lbo)
+    return fail(MCX_ERR_ARG, "%s needs the whole table on one device, not a graph split over devices%s", what, why);
+  if (g->hidden >= 0) return fail(MCX_ERR_ARG, "%s does not take a graph in intersect mode", what);
+  return MCX_OK;
+}
+
 // ---------------------------------------------------------------------------
 // inferedges (ctx_infer_edges.c, infer_edges.c): records against the loaded table, mcx_infer.h
 // ---------------------------------------------------------------------------
@@ -3135,17 +3147,14 @@ extern "C" int mcx_graph_add_records(mcx_graph *g, const void *recs, uint64_t nr
 // and the call's counters are zeroed.
 static int infer_begin(mcx_graph *g, const void *recs, uint64_t nrecs, int ncols, uint32_t flags)
 {
-  if (!g) return fail(MCX_ERR_ARG, "null graph");
-  if (g->as_group || g->group || g->t.lbo || g->own_lbo)
-    return fail(MCX_ERR_ARG, "inferedges needs the whole table on one device, not a graph split over devices");
-  if (g->hidden >= 0) return fail(MCX_ERR_ARG, "inferedges does not take a graph in intersect mode");
+  int rc = whole_table_only(g, "inferedges", "");
+  if (rc != MCX_OK) return rc;
   if (ncols != g->ncols) return fail(MCX_ERR_ARG, "the records have %d colours, the graph %d", ncols, g->ncols);
   if (flags & ~(uint32_t)(MCX_INFER_POP | MCX_INFER_PRESENCE_COVG)) return fail(MCX_ERR_ARG, "unknown inferedges flags 0x%x", flags);
   if (!infer_tile_recs(8u * g->W + 5u * (uint32_t)ncols)) return fail(MCX_ERR_ARG, "too many colours for inferedges: %d", ncols);
   if (nrecs && !recs) return fail(MCX_ERR_ARG, "null records");
   HIP_TRY(hipSetDevice(g->device));
-  int rc = fetch_counters(g);
-  if (rc != MCX_OK) return rc;
+  if ((rc = fetch_counters(g)) != MCX_OK) return rc;
   if (!g->d_infer) HIP_TRY(hipMalloc((void **)&g->d_infer, 2 * sizeof(unsigned long long)));
   HIP_TRY(hipMemsetAsync(g->d_infer, 0, 2 * sizeof(unsigned long long), g->stream));
   return MCX_OK;
@@ -3264,13 +3273,10 @@ static void clean_drop(mcx_graph *g)
 // the refusals and the closing flush; *n = k-mers in the table; `what` names the command in the messages
 static int clean_begin(mcx_graph *g, uint64_t *n, const char *what)
 {
-  if (!g) return fail(MCX_ERR_ARG, "null graph");
-  if (g->as_group || g->group || g->t.lbo || g->own_lbo)
-    return fail(MCX_ERR_ARG, "%s needs the whole table on one device, not a graph split over devices (unitigs cross shards)", what);
-  if (g->hidden >= 0) return fail(MCX_ERR_ARG, "%s does not take a graph in intersect mode", what);
-  HIP_TRY(hipSetDevice(g->device));
-  int rc = fetch_counters(g);
+  int rc = whole_table_only(g, what, " (unitigs cross shards)");
   if (rc != MCX_OK) return rc;
+  HIP_TRY(hipSetDevice(g->device));
+  if ((rc = fetch_counters(g)) != MCX_OK) return rc;
   *n = g->h_ctr->novel;
   if (*n >= (1ull << 31)) return fail(MCX_ERR_ARG, "%s takes graphs of fewer than 2^31 k-mers (%llu)", what, (unsigned long long)*n);
   return MCX_OK;
@@ -3666,9 +3672,8 @@ extern "C" int mcx_graph_subgraph_seed_stream_dev(mcx_graph *g, const void *d_st
   return subgraph_seed_launch(g, L);
 }
 
-// Host seeds through the pinned staging buffers, in the chunk layout of the ASCII path of mcx_graph_add_reads: kCarry
-// positions carried over from the chunk before, then whole reads each followed by a separator (or a piece of a read
-// longer than a chunk); a chunk owns the k-mers that start kCarry - k positions in up to k before its end.
+// Host seeds through the pinned staging buffers, in the carry layout of mcx_chunk.h (that of the ASCII path of
+// mcx_graph_add_reads); a chunk owns the k-mers that start kCarry - k positions in up to k before its end.
 extern "C" int mcx_graph_subgraph_seed_reads(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads)
 {
   if (!g) return fail(MCX_ERR_ARG, "null graph");
@@ -3679,40 +3684,14 @@ extern "C" int mcx_graph_subgraph_seed_reads(mcx_graph *g, const uint8_t *bases,
   int rc = ensure_stage(g);
   if (rc != MCX_OK) return rc;
   // new bytes per chunk: the staging buffers are sized for the packed layout of mcx_graph_add_reads by default, which is
-  // smaller than kCarry + kStageBytes + 64 ASCII bytes, so a chunk is bounded by what a buffer holds
-  const uint64_t cap = std::min<uint64_t>(kStageBytes, g->stage_alloc - kCarry - 64);
-  uint64_t r = 0, r_pos = 0;  // next read, bytes of it already staged
-  uint8_t carry[kCarry];
-  memset(carry, '\n', kCarry);
-  while (r < nreads) {
-    const int b = g->cur;
-    g->cur = (g->cur + 1) % mcx_graph::kStageBufs;
-    HIP_TRY(hipEventSynchronize(g->ev[b]));  // previous use of this buffer finished
-    uint8_t *hs = g->h_stage[b];
-    memcpy(hs, carry, kCarry);
-    uint64_t L = 0;
-    while (r < nreads) {
-      const uint64_t len = off[r + 1] - off[r], remain = len - r_pos;
-      if (r_pos == 0 && remain + 1 <= cap - L) {
-        memcpy(hs + kCarry + L, bases + off[r], len);
-        L += len;
-        hs[kCarry + L++] = '\n';
-        r++;
-      } else if (L == 0) {  // a read longer than a chunk (or its tail): a piece on its own
-        const uint64_t take = std::min(remain, cap - 1);
-        memcpy(hs + kCarry, bases + off[r] + r_pos, take);
-        L = take;
-        r_pos += take;
-        if (r_pos == len) { hs[kCarry + L++] = '\n'; r++; r_pos = 0; }
-        break;
-      } else {
-        break;
-      }
-    }
-    const uint64_t total = kCarry + L;
-    memcpy(carry, hs + total - kCarry, kCarry);
-    memset(hs + total, '\n', 64);  // the 16-byte chunk loads of the kernel stay inside the copy
-    HIP_TRY(hipMemcpyAsync(g->d_stage[b], hs, total + 64, hipMemcpyHostToDevice, g->stream));
+  // smaller than kCarry + kStageBytes + kChunkPad ASCII bytes, so a chunk is bounded by what a buffer holds
+  const ChunkLayout lay{kCarry, std::min<uint64_t>(kStageBytes, g->stage_alloc - kCarry - kChunkPad), ~0ull, 0, false};
+  ReadChunker ck(bases, off, nreads);
+  while (!ck.done()) {
+    int b;
+    if ((rc = next_stage(g, &b)) != MCX_OK) return rc;
+    const uint64_t total = kCarry + ck.fill(lay, g->h_stage[b], nullptr).L;
+    HIP_TRY(hipMemcpyAsync(g->d_stage[b], g->h_stage[b], total + kChunkPad, hipMemcpyHostToDevice, g->stream));  // (the pad: the kernel's 16-byte loads stay inside the copy)
     StreamLaunch SL{g->d_stage[b], total, kCarry - (uint64_t)g->k, total - (uint64_t)g->k, nullptr};
     rc = subgraph_seed_launch(g, SL);
     HIP_TRY(hipEventRecord(g->ev[b], g->stream));
@@ -3801,12 +3780,11 @@ extern "C" int mcx_graph_subgraph_finish(mcx_graph *g, uint32_t dist, uint32_t f
 // ---------------------------------------------------------------------------
 // reads (ctx_reads.c): which reads share a k-mer with the graph -- mcx_reads.h
 // ---------------------------------------------------------------------------
-static int reads_touch_begin(mcx_graph *g)
+// what `reads` and `coverage` (`what` in the messages) share: the refusals, the call's counters and the closing flush
+static int lookup_begin(mcx_graph *g, const char *what)
 {
-  if (!g) return fail(MCX_ERR_ARG, "null graph");
-  if (g->as_group || g->group || g->t.lbo || g->own_lbo)
-    return fail(MCX_ERR_ARG, "reads needs the whole table on one device, not a graph split over devices (a read's k-mers are on every shard)");
-  if (g->hidden >= 0) return fail(MCX_ERR_ARG, "reads does not take a graph in intersect mode");
+  int rc = whole_table_only(g, what, " (a read's k-mers are on every shard)");
+  if (rc != MCX_OK) return rc;
   HIP_TRY(hipSetDevice(g->device));
   if (!g->d_rt_cnt) {
     HIP_TRY(hipMalloc((void **)&g->d_rt_cnt, 2 * sizeof(unsigned long long)));
@@ -3829,7 +3807,7 @@ static int reads_touch_launch(mcx_graph *g, const uint8_t *d_stream, uint64_t nb
 extern "C" int mcx_graph_reads_touch_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes, const void *d_stream_off, uint64_t nreads,
                                                 void *d_hit)
 {
-  int rc = reads_touch_begin(g);
+  int rc = lookup_begin(g, "reads");
   if (rc != MCX_OK) return rc;
   if (((uintptr_t)d_stream & 15) != 0) return fail(MCX_ERR_ARG, "stream must be 16-byte aligned");
   if (((uintptr_t)d_stream_off & 7) != 0) return fail(MCX_ERR_ARG, "stream offsets must be 8-byte aligned");
@@ -3847,27 +3825,38 @@ extern "C" int mcx_graph_reads_touch_stream_dev(mcx_graph *g, const void *d_stre
   return reads_touch_launch(g, (const uint8_t *)d_stream, nbytes, (const uint64_t *)d_stream_off, nreads, g->d_rt_mask, (uint8_t *)d_hit);
 }
 
-// Host reads through the pinned staging buffers as ASCII.  A chunk stands alone: whole reads each followed by a
-// separator, or ONE piece of a read that does not fit a chunk, also followed by a separator; consecutive pieces overlap
-// by k - 1 bases, so every k-mer of the read starts in exactly one piece, and the read's byte is the OR of its pieces'.
+// The stand-alone chunks (mcx_chunk.h) of `reads` and `coverage` (`what` in the message): a staging buffer is
+// [0, C) stream | offsets (R + 1) | the command's own regions, R = C / 16 reads at most.  C is what a chunk holds by
+// default or the reads_chunk knob, a multiple of 64 and at least 256, and at most num / den of the buffer less `fixed`
+// bytes: what the command's regions leave.  Buffers of less than min_alloc bytes are refused.
+static int alone_layout(const mcx_graph *g, const char *what, uint64_t min_alloc, uint64_t fixed, uint64_t num, uint64_t den, ChunkLayout *lay)
+{
+  const uint64_t S = g->stage_alloc;
+  uint64_t C = (std::min<uint64_t>(kStageBytes, g->reads_chunk ? g->reads_chunk : ~0ull) + 63) / 64 * 64;
+  if (S < min_alloc) return fail(MCX_ERR_ARG, "%s: the staging buffers (%llu bytes) are too small", what, (unsigned long long)S);
+  C = std::max<uint64_t>(256, std::min<uint64_t>(C, ((S - fixed) * num / den) & ~63ull));
+  *lay = ChunkLayout{0, C, C / 16, (uint64_t)g->k - 1, true};
+  return MCX_OK;
+}
+
+// Host reads through the pinned staging buffers as ASCII, in the stand-alone chunks of mcx_chunk.h: every k-mer of a
+// read in pieces starts in exactly one piece, and the read's byte is the OR of its pieces'.
 // One staging pair holds everything of a chunk: stream, offsets, the hit bytes coming back (pinned on the host side)
 // and, on the device side only, the hit masks.
 extern "C" int mcx_graph_reads_touch(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, uint8_t *hit,
                                      mcx_touch_stats *stats_accum)
 {
-  int rc = reads_touch_begin(g);
+  int rc = lookup_begin(g, "reads");
   if (rc != MCX_OK) return rc;
   if (nreads && (!off || !hit)) return fail(MCX_ERR_ARG, "null read buffers");
   if (!nreads) return MCX_OK;
   if (!bases && off[nreads] != off[0]) return fail(MCX_ERR_ARG, "null read buffers");
   if ((rc = ensure_stage(g)) != MCX_OK) return rc;
   // layout: [0, C) stream | offsets (R + 1) | hit bytes R | masks, 512 bytes per tile; R = C / 16 reads at most
-  const uint64_t S = g->stage_alloc;
-  uint64_t C = (std::min<uint64_t>(kStageBytes, g->reads_chunk ? g->reads_chunk : ~0ull) + 63) / 64 * 64;
-  if (S < 704 + 256 * 27 / 16) return fail(MCX_ERR_ARG, "reads: the staging buffers (%llu bytes) are too small", (unsigned long long)S);
-  C = std::max<uint64_t>(256, std::min<uint64_t>(C, ((S - 704) * 16 / 27) & ~63ull));
-  const uint64_t R = C / 16, off_at = C, hit_at = (off_at + 8 * (R + 1) + 15) & ~15ull, mask_at = (hit_at + R + 63) & ~63ull;
-  if (mask_at + (C + kTile - 1) / kTile * (kTile / 8) > S) return fail(MCX_ERR_HIP, "reads: internal error in the staging layout");
+  ChunkLayout lay;
+  if ((rc = alone_layout(g, "reads", 704 + 256 * 27 / 16, 704, 16, 27, &lay)) != MCX_OK) return rc;
+  const uint64_t C = lay.cap, R = lay.max_reads, off_at = C, hit_at = (off_at + 8 * (R + 1) + 15) & ~15ull, mask_at = (hit_at + R + 63) & ~63ull;
+  if (mask_at + (C + kTile - 1) / kTile * (kTile / 8) > g->stage_alloc) return fail(MCX_ERR_HIP, "reads: internal error in the staging layout");
   hipStream_t st = g->stream;
   HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
   memset(hit, 0, nreads);
@@ -3877,39 +3866,15 @@ extern "C" int mcx_graph_reads_touch(mcx_graph *g, const uint8_t *bases, const u
     for (uint64_t j = 0; j < inflight[b].n; j++) hit[inflight[b].r0 + j] |= h[j];
     inflight[b].n = 0;
   };
-  const uint64_t k1 = (uint64_t)g->k - 1;
-  uint64_t r = 0, r_pos = 0;  // next read, first base of it that the next piece starts with
-  while (r < nreads) {
-    const int b = g->cur;
-    g->cur = (g->cur + 1) % mcx_graph::kStageBufs;
-    HIP_TRY(hipEventSynchronize(g->ev[b]));  // previous use of this buffer finished
+  ReadChunker ck(bases, off, nreads);
+  while (!ck.done()) {
+    int b;
+    if ((rc = next_stage(g, &b)) != MCX_OK) return rc;
     harvest(b);
     uint8_t *hs = g->h_stage[b];
     uint64_t *ho = reinterpret_cast<uint64_t *>(hs + off_at);
-    uint64_t L = 0, n = 0;
-    const uint64_t r0 = r;
-    ho[0] = 0;
-    while (r < nreads && n < R) {
-      const uint64_t len = off[r + 1] - off[r];
-      if (r_pos == 0 && len + 1 <= C - L) {
-        if (len) memcpy(hs + L, bases + off[r], len);
-        L += len;
-        hs[L++] = '\n';
-        ho[++n] = L;
-        r++;
-      } else if (L == 0) {  // a read longer than a chunk: a piece on its own
-        const uint64_t take = std::min(len - r_pos, C - 1);
-        memcpy(hs, bases + off[r] + r_pos, take);
-        L = take;
-        hs[L++] = '\n';
-        ho[++n] = L;
-        if (r_pos + take == len) { r++; r_pos = 0; }
-        else r_pos += take - k1;
-        break;
-      } else {
-        break;
-      }
-    }
+    const Chunk c = ck.fill(lay, hs, ho);
+    const uint64_t L = c.L, n = c.n;
     uint8_t *ds = g->d_stage[b];
     HIP_TRY(hipMemcpyAsync(ds, hs, L, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ds + off_at, ho, 8 * (n + 1), hipMemcpyHostToDevice, st));
@@ -3917,7 +3882,7 @@ extern "C" int mcx_graph_reads_touch(mcx_graph *g, const uint8_t *bases, const u
     if (rc != MCX_OK) return rc;
     HIP_TRY(hipMemcpyAsync(hs + hit_at, ds + hit_at, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(g->ev[b], st));
-    inflight[b].r0 = r0;
+    inflight[b].r0 = c.r0;
     inflight[b].n = n;
   }
   unsigned long long h[2] = {0, 0};
@@ -3938,20 +3903,6 @@ extern "C" int mcx_graph_reads_touch(mcx_graph *g, const uint8_t *bases, const u
 // ---------------------------------------------------------------------------
 // coverage (ctx_coverage.c): what the table stores for the k-mers of reads -- mcx_coverage.h
 // ---------------------------------------------------------------------------
-static int coverage_begin(mcx_graph *g)
-{
-  if (!g) return fail(MCX_ERR_ARG, "null graph");
-  if (g->as_group || g->group || g->t.lbo || g->own_lbo)
-    return fail(MCX_ERR_ARG, "coverage needs the whole table on one device, not a graph split over devices (a read's k-mers are on every shard)");
-  if (g->hidden >= 0) return fail(MCX_ERR_ARG, "coverage does not take a graph in intersect mode");
-  HIP_TRY(hipSetDevice(g->device));
-  if (!g->d_rt_cnt) {
-    HIP_TRY(hipMalloc((void **)&g->d_rt_cnt, 2 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), g->stream));
-  }
-  return flush_deferred(g);  // the lookups see every insert made so far
-}
-
 // pass A over one stream (positions [0, nbytes)) into arrays of `pitch` positions per colour, on the handle's stream
 static int coverage_probe(mcx_graph *g, const uint8_t *d_stream, uint64_t nbytes, uint32_t *d_covg, uint8_t *d_edges, uint64_t pitch)
 {
@@ -3963,7 +3914,7 @@ static int coverage_probe(mcx_graph *g, const uint8_t *d_stream, uint64_t nbytes
 
 extern "C" int mcx_graph_coverage_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes, void *d_covg, void *d_edges, uint64_t pitch)
 {
-  int rc = coverage_begin(g);
+  int rc = lookup_begin(g, "coverage");
   if (rc != MCX_OK) return rc;
   if (((uintptr_t)d_stream & 15) != 0) return fail(MCX_ERR_ARG, "stream must be 16-byte aligned");
   if (((uintptr_t)d_covg & 15) != 0 || ((uintptr_t)d_edges & 15) != 0) return fail(MCX_ERR_ARG, "coverage: the output arrays must be 16-byte aligned");
@@ -3984,10 +3935,9 @@ struct CvBatch {
   unsigned long long cnt[2] = {0, 0};
 };
 
-// Host reads through the pinned staging buffers as ASCII, chunked as mcx_graph_reads_touch chunks them: whole reads each
-// followed by a separator, or one piece of a read that does not fit a chunk; consecutive pieces overlap by k - 1 bases
-// and a piece owns the k-mers that start in it, that is all its positions but the last k - 1 (the last piece owns all
-// of its own).  A chunk is probed into scratch arrays indexed by its stream position and placed from there into the
+// Host reads through the pinned staging buffers as ASCII, in the stand-alone chunks of mcx_chunk.h: a piece owns the
+// k-mers that start in it, that is all its positions but the last k - 1 (the last piece of a read owns all of its
+// own).  A chunk is probed into scratch arrays indexed by its stream position and placed from there into the
 // batch's.  Synchronous.
 static int coverage_batch(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, bool want_edges, CvBatch &B)
 {
@@ -3997,12 +3947,10 @@ static int coverage_batch(mcx_graph *g, const uint8_t *bases, const uint64_t *of
   const uint64_t ncols = (uint64_t)g->ncols, nbases = off[nreads] - off[0];
   B.pitch = std::max<uint64_t>(64, (nbases + 63) / 64 * 64);
   // layout of a staging buffer: [0, C) stream | offsets (R + 1); R = C / 16 reads at most
-  const uint64_t S = g->stage_alloc;
-  uint64_t C = (std::min<uint64_t>(kStageBytes, g->reads_chunk ? g->reads_chunk : ~0ull) + 63) / 64 * 64;
-  if (S < 1024) return fail(MCX_ERR_ARG, "coverage: the staging buffers (%llu bytes) are too small", (unsigned long long)S);
-  C = std::max<uint64_t>(256, std::min<uint64_t>(C, ((S - 64) * 2 / 3) & ~63ull));
-  const uint64_t R = C / 16, off_at = C;
-  if (off_at + 8 * (R + 1) > S) return fail(MCX_ERR_HIP, "coverage: internal error in the staging layout");
+  ChunkLayout lay;
+  if ((rc = alone_layout(g, "coverage", 1024, 64, 2, 3, &lay)) != MCX_OK) return rc;
+  const uint64_t C = lay.cap, R = lay.max_reads, off_at = C;
+  if (off_at + 8 * (R + 1) > g->stage_alloc) return fail(MCX_ERR_HIP, "coverage: internal error in the staging layout");
   const uint64_t spitch = C;  // (a multiple of 64)
   DevBuf<uint32_t> scovg;
   DevBuf<uint8_t> sedges;
@@ -4013,45 +3961,21 @@ static int coverage_batch(mcx_graph *g, const uint8_t *bases, const uint64_t *of
   if (want_edges) HIP_TRY(sedges.alloc(ncols * spitch));
   HIP_TRY(hipMemcpyAsync(B.off, off, 8 * (nreads + 1), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
-  const uint64_t k1 = (uint64_t)g->k - 1;
-  uint64_t r = 0, r_pos = 0;  // next read, first base of it that the next piece starts with
+  ReadChunker ck(bases, off, nreads);
   auto run = [&]() -> int {
-    while (r < nreads) {
-      const int b = g->cur;
-      g->cur = (g->cur + 1) % mcx_graph::kStageBufs;
-      HIP_TRY(hipEventSynchronize(g->ev[b]));  // previous use of this buffer finished
+    while (!ck.done()) {
+      int b;
+      int rc2 = next_stage(g, &b);
+      if (rc2 != MCX_OK) return rc2;
       uint8_t *hs = g->h_stage[b];
       uint64_t *ho = reinterpret_cast<uint64_t *>(hs + off_at);
-      uint64_t L = 0, n = 0, shift = 0, own = ~0ull;
-      const uint64_t r0 = r;
-      ho[0] = 0;
-      while (r < nreads && n < R) {
-        const uint64_t len = off[r + 1] - off[r];
-        if (r_pos == 0 && len + 1 <= C - L) {
-          if (len) memcpy(hs + L, bases + off[r], len);
-          L += len;
-          hs[L++] = '\n';
-          ho[++n] = L;
-          r++;
-        } else if (L == 0) {  // a read longer than a chunk: a piece on its own
-          const uint64_t take = std::min(len - r_pos, C - 1);
-          memcpy(hs, bases + off[r] + r_pos, take);
-          L = take;
-          hs[L++] = '\n';
-          ho[++n] = L;
-          shift = r_pos;
-          if (r_pos + take == len) { r++; r_pos = 0; }
-          else { own = take - k1; r_pos += take - k1; }
-          break;
-        } else {
-          break;
-        }
-      }
+      const Chunk c = ck.fill(lay, hs, ho);
+      const uint64_t L = c.L, n = c.n, r0 = c.r0, shift = c.shift;
+      const uint64_t own = c.piece_of >= 0 && !c.ended ? c.take - lay.overlap : ~0ull;  // (whole reads and last pieces own all of their own)
       uint8_t *ds = g->d_stage[b];
       HIP_TRY(hipMemcpyAsync(ds, hs, L, hipMemcpyHostToDevice, st));
       HIP_TRY(hipMemcpyAsync(ds + off_at, ho, 8 * (n + 1), hipMemcpyHostToDevice, st));
-      int rc2 = coverage_probe(g, ds, L, scovg, sedges, spitch);
-      if (rc2 != MCX_OK) return rc2;
+      if ((rc2 = coverage_probe(g, ds, L, scovg, sedges, spitch)) != MCX_OK) return rc2;
       GRID_LAUNCH(k_cv_place, L, reinterpret_cast<const uint64_t *>(ds + off_at), n, (const uint64_t *)B.off.p, r0, shift, own, (uint32_t)ncols,
                   (const uint32_t *)scovg.p, (const uint8_t *)sedges.p, spitch, B.covg.p, B.edges.p, B.pitch);
       HIP_TRY(hipEventRecord(g->ev[b], st));
@@ -4076,7 +4000,7 @@ static void coverage_add_stats(mcx_coverage_stats *s, uint64_t nreads, const CvB
 extern "C" int mcx_graph_coverage(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, uint32_t *covg, uint8_t *edges,
                                   mcx_coverage_stats *stats_accum)
 {
-  int rc = coverage_begin(g);
+  int rc = lookup_begin(g, "coverage");
   if (rc != MCX_OK) return rc;
   if (!nreads) return MCX_OK;
   if (!off || !covg) return fail(MCX_ERR_ARG, "null read buffers");
@@ -4100,7 +4024,7 @@ extern "C" int mcx_graph_coverage(mcx_graph *g, const uint8_t *bases, const uint
 extern "C" int mcx_graph_coverage_text(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, uint32_t flags, mcx_sink_fn sink,
                                        void *ctx, uint64_t *line_off, mcx_coverage_stats *stats_accum)
 {
-  int rc = coverage_begin(g);
+  int rc = lookup_begin(g, "coverage");
   if (rc != MCX_OK) return rc;
   if (flags & ~(uint32_t)(MCX_COVERAGE_EDGES | MCX_COVERAGE_DEGREES)) return fail(MCX_ERR_ARG, "coverage: unknown flags 0x%x", flags);
   if (!nreads) { if (line_off) line_off[0] = 0; return MCX_OK; }
@@ -4128,22 +4052,13 @@ extern "C" int mcx_graph_coverage_text(mcx_graph *g, const uint8_t *bases, const
   if (line_off) HIP_TRY(hipMemcpyAsync(line_off, loff.p, 8 * (nlines + 1), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));  // the text is complete, the staging buffers are ours
   HIP_TRY(hipStreamSynchronize(g->cstream));
-  // chunk i + 1 is copied out while chunk i is with the sink
   const uint64_t chunk = std::min<uint64_t>(kStageBytes, g->stage_alloc) & ~15ull;
   auto fetch = [&](uint64_t c0, int b) -> int {
     HIP_TRY(hipMemcpyAsync(g->h_stage[b], text.p + c0, std::min(total, c0 + chunk) - c0, hipMemcpyDeviceToHost, g->cstream));
     HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
     return MCX_OK;
   };
-  if (total) rc = fetch(0, 0);
-  int b = 0;
-  for (uint64_t c0 = 0; c0 < total && rc == MCX_OK; c0 += chunk, b ^= 1) {
-    if (c0 + chunk < total && (rc = fetch(c0 + chunk, b ^ 1)) != MCX_OK) break;
-    HIP_TRY(hipEventSynchronize(g->ev_copy[b]));
-    if (sink(ctx, g->h_stage[b], (size_t)(std::min(total, c0 + chunk) - c0)) != 0) rc = fail(MCX_ERR_SINK, "coverage sink failed");
-  }
-  (void)hipStreamSynchronize(g->cstream);  // leave nothing in flight on the staging buffers, nor on the text
-  if (rc != MCX_OK) return rc;
+  if ((rc = drain_to_sink(g, total, chunk, fetch, sink, ctx, "coverage sink failed")) != MCX_OK) return rc;  // (nothing is left in flight on the text either)
   coverage_add_stats(stats_accum, nreads, B);
   return MCX_OK;
 }
@@ -4342,18 +4257,8 @@ extern "C" int mcx_graph_unitigs(mcx_graph *g, int format, uint32_t flags, mcx_s
     HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
     return MCX_OK;
   };
-  // chunk i + 1 is emitted while chunk i is copied out and handed to the sink; a buffer is emitted into again only
-  // after the sink has returned from it
   double t0 = now_s();
-  if (total) rc = produce(0, 0);
-  int b = 0;
-  for (uint64_t c0 = 0; c0 < total && rc == MCX_OK; c0 += chunk, b ^= 1) {
-    if (c0 + chunk < total && (rc = produce(c0 + chunk, b ^ 1)) != MCX_OK) break;
-    HIP_TRY(hipEventSynchronize(g->ev_copy[b]));
-    if (sink(ctx, g->h_stage[b], (size_t)(std::min(total, c0 + chunk) - c0)) != 0) rc = fail(MCX_ERR_SINK, "unitigs sink failed");
-  }
-  (void)hipStreamSynchronize(st);  // leave nothing in flight on the staging buffers
-  (void)hipStreamSynchronize(g->cstream);
+  rc = drain_to_sink(g, total, chunk, produce, sink, ctx, "unitigs sink failed");
   phase_clock("unitigs", "text emitted and delivered", t0);
   if (rc != MCX_OK) return rc;
   if (stats) { stats->num_unitigs = w.nu; stats->num_kmers = w.n; stats->num_bytes = total; stats->num_cycles = w.ncycles; }
