@@ -515,6 +515,67 @@ int mcx_graph_coverage_stream_dev(mcx_graph *g, const void *d_stream, uint64_t n
 int mcx_graph_coverage_text(mcx_graph *g, const uint8_t *bases, const uint64_t *read_offsets, uint64_t nreads, uint32_t flags,
                             mcx_sink_fn sink, void *ctx, uint64_t *line_off, mcx_coverage_stats *stats_accum /* optional, += */);
 
+/* `correct` (src/commands/ctx_correct.c; correct_aln_read, handle_read2) without link files: reads corrected against the
+ * graph.  The k-mers of a read are those of `reads` above.  Graph view (ctx_correct.c:116-121, 187): every key of the
+ * table is walked, a k-mer's edges are the OR of its edge bytes over all colours, and a k-mer is in the sample iff its
+ * value word in `colour` is non-zero (coverage or edges, the presence rule of `inferedges` below).
+ *   Alignment (db_alignment_from_read): a k-mer aligns iff it is a key and in the sample.  Aligned k-mers at consecutive
+ *       positions stay in one segment while the union edges of the earlier hold the edge to the later; a missing edge
+ *       ends the contig with no traversal (db_alignment_next_gap, correct_alignment_nxt:390).
+ *   Walker step (graph_walker_choose:385-433 with no paths held): the successors over the union edges in nucleotide order;
+ *       none: stop; one: take it, POPFWD if it is not in the sample; several: those in the sample, exactly one: take it,
+ *       otherwise stop.  The reference asserts that an edge never names an absent k-mer; here such an edge counts as no
+ *       edge.  A walk enters an oriented node twice at the most, the third entry stops it (repeat_walker.h:18-50 with
+ *       graph_walker_hash64 of (node, orient) alone); every walk starts clean: the visited bits the reference leaves
+ *       behind after a POPFWD stop and the false positives of its 22-bit Bloom filter are not reproduced.
+ *   Gaps (correct_alignment_nxt:402-438): gap_est = the distance of the two positions, wiggle = (long)(gap_est *
+ *       gap_variance + gap_wiggle) in float arithmetic, gap_min = max(0, est - wiggle), gap_max = est + wiggle.  One way
+ *       (traverse_one_way2): forward from the node before the gap for gap_max + 1 nodes at the most, stopping on a POPFWD
+ *       step, done on reaching the node behind the gap with gap_len >= gap_min; on failure the same from the reverse of
+ *       the node behind the gap.  MCX_CORRECT_TWO_WAY (traverse_two_way2:208-236): two walkers step in turn.  A failed
+ *       gap ends the contig.
+ *   Ends (correct_aln_read:570-639): the left end is extended by at most the first position, the right end by at most
+ *       len - (last position + k) steps; POPFWD steps are accepted.  Reads that align perfectly and reads with no aligned
+ *       k-mer skip gaps and ends.
+ *   Record (handle_read2): uncorrectable stretches in lower case, aligned k-mers and filled bases in upper case (the
+ *       nprint rule of correct_reads.c:170-194 says how many filled bases a gap prints), then, if quals is not NULL, as
+ *       many quality bytes: the read's own for its bases, fq_zero (0: '.') for filled ones.  Record r is bytes
+ *       [out_off[r], out_off[r + 1]) of what reaches `sink` in consecutive ranges, in input order.
+ * mcx_graph_correct takes the layout of mcx_graph_add_reads; quals, if given, has a byte per base.  Flushes pending
+ * inserts first.  Synchronous.  The reads go through the pinned staging buffers in the chunks of mcx_graph_coverage
+ * ("reads_chunk"), and a read in pieces is whole on the device before its walks are made.  Every gap walk and every end
+ * extension is an independent task of four lanes.  HBM: 9 (+ 1 with qualities) bytes per base of the batch, 9 bytes per
+ * path entry of the tasks (gap_max + 2 per gap, the limit per end) and the records; MCX_ERR_NOMEM when that does not
+ * fit.  The result is a function of the table's contents, the reads and the parameters alone, not of the table's size
+ * or load, the chunking or the "grid" knob.  The table is only read.  nreads == 0 is MCX_OK.
+ * mcx_graph_correct_stream_dev runs the probe, the tasks and the walks over a stream in HBM with the layout of
+ * mcx_graph_reads_touch_stream_dev (for the benchmark tool): d_node is scratch of `pitch` 64-bit words, 16-byte aligned,
+ * pitch a multiple of 64 and at least nbytes; d_len receives the nreads record lengths.  It hands out no records and
+ * returns when the walks are done (their scratch is sized by two totals read back from the device).
+ * Stats: gaps = gaps_filled + gaps_too_short + gaps_too_long_or_stopped, each gap by the walk that decided it (too
+ * short: gap_len < gap_min).  stops_* count over the walks of every kind what made a walker's last step fail: several
+ * successors and not exactly one in the sample, a POPFWD step inside a gap, a third entry.  missing_edges counts, as
+ * the reference does, only the first of a perfectly aligned read.  bases_filled = bytes written with fq_zero quality.
+ * Refusals (MCX_ERR_ARG): a graph split over devices, a handle in intersect mode, colour >= ncols, unknown flags, a
+ * negative or non-finite gap_variance / gap_wiggle. */
+enum { MCX_CORRECT_TWO_WAY = 1 };
+typedef struct { uint32_t colour, flags; float gap_variance /* D, 0.1 */, gap_wiggle /* d, 5 */; char fq_zero; } mcx_correct_params;
+typedef struct {
+  uint64_t num_reads, num_kmers, num_kmers_found, num_perfect, num_no_kmers;
+  uint64_t gaps, gaps_filled, gaps_filled_backward, gaps_too_short, gaps_too_long_or_stopped;
+  uint64_t stops_fork, stops_colour, stops_repeat, missing_edges;
+  uint64_t end_gaps, end_gaps_extended, bases_filled;
+} mcx_correct_stats;
+int mcx_graph_correct(mcx_graph *g, const uint8_t *bases, const uint8_t *quals /* or NULL */, const uint64_t *read_offsets,
+                      uint64_t nreads, const mcx_correct_params *p, mcx_sink_fn sink, void *ctx,
+                      uint64_t *out_off /* nreads + 1, or NULL */, mcx_correct_stats *stats_accum /* optional, += */);
+int mcx_graph_correct_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes, const void *d_stream_off /* nreads+1 u64 */,
+                                 uint64_t nreads, const mcx_correct_params *p, void *d_node /* pitch u64 */, uint64_t pitch,
+                                 void *d_len /* nreads u64 */, mcx_correct_stats *stats_accum /* optional, += */);
+/* walker steps (one per lookup round of a walker) of the last of the two calls on this handle: what the benchmark tool
+ * divides by k_cr_walk's time */
+uint64_t mcx_graph_correct_walk_steps(const mcx_graph *g);
+
 /* `inferedges`: infer_kmer_edges (src/tools/infer_edges.c) for every record of `recs` (.ctx body
  * layout, ncols == the graph's colours) against the k-mers loaded into the graph.  Each edge that some
  * colour lacks (default, --all) or that some colour has and another lacks (MCX_INFER_POP, --pop)

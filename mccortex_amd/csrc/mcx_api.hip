@@ -35,6 +35,7 @@
 #include "mcx_subgraph.h"
 #include "mcx_reads.h"
 #include "mcx_coverage.h"
+#include "mcx_correct.h"
 #include "mcx_chunk.h"
 
 using namespace mcx;
@@ -306,6 +307,7 @@ struct mcx_graph {
   unsigned long long *d_rt_cnt = nullptr;  // [k-mer occurrences probed, occurrences found] of the current host call
   uint64_t *d_rt_mask = nullptr;           // hit masks of the device entry, 1 bit per stream position (grows, never shrinks)
   uint64_t rt_mask_bytes = 0;
+  uint64_t cr_walk_steps = 0;              // walker steps of the last `correct` call (mcx_graph_correct_walk_steps)
   uint64_t reads_chunk = 0;                // test knob: stream bytes per chunk of mcx_graph_reads_touch and of coverage_batch (0 = what a staging buffer holds)
 };
 
@@ -4060,6 +4062,217 @@ extern "C" int mcx_graph_coverage_text(mcx_graph *g, const uint8_t *bases, const
   };
   if ((rc = drain_to_sink(g, total, chunk, fetch, sink, ctx, "coverage sink failed")) != MCX_OK) return rc;  // (nothing is left in flight on the text either)
   coverage_add_stats(stats_accum, nreads, B);
+  return MCX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// correct (ctx_correct.c): reads corrected against the graph -- mcx_correct.h
+// ---------------------------------------------------------------------------
+static int correct_begin(mcx_graph *g, const mcx_correct_params *p, mcx_correct_params *q)
+{
+  int rc = lookup_begin(g, "correct");
+  if (rc != MCX_OK) return rc;
+  if (!p) return fail(MCX_ERR_ARG, "correct: null parameters");
+  if (p->colour >= (uint32_t)g->ncols) return fail(MCX_ERR_ARG, "correct: colour %u is not one of the graph's %d", p->colour, g->ncols);
+  if (p->flags & ~(uint32_t)MCX_CORRECT_TWO_WAY) return fail(MCX_ERR_ARG, "correct: unknown flags 0x%x", p->flags);
+  if (!std::isfinite(p->gap_variance) || !std::isfinite(p->gap_wiggle) || p->gap_variance < 0 || p->gap_wiggle < 0)
+    return fail(MCX_ERR_ARG, "correct: the gap variance and the gap wiggle must be finite and not negative");
+  *q = *p;
+  if (!q->fq_zero) q->fq_zero = '.';
+  return MCX_OK;
+}
+
+// pass A over one stream (positions [0, nbytes)) into `pitch` node references, on the handle's stream
+static int correct_probe(mcx_graph *g, const uint8_t *d_stream, uint64_t nbytes, uint32_t colour, uint64_t *d_node, uint64_t pitch)
+{
+  hipStream_t st = g->stream;
+  const StreamArgs a = make_args(g, StreamLaunch{d_stream, nbytes, 0, nbytes, nullptr});
+  if (a.ntiles) GRID_LAUNCH_W(k_cr_probe, a.ntiles * (uint64_t)kThreads, a, g->t, colour, pitch, d_node, g->d_rt_cnt);
+  return MCX_OK;
+}
+
+// what passes B and C leave for the records: the tasks of every read, what the walks made of them, the counters
+struct CrWork {
+  DevBuf<uint64_t> toff, coff, refs;
+  DevBuf<CrTask> tasks;
+  DevBuf<CrRes> res;
+  DevBuf<uint8_t> codes;
+  DevBuf<unsigned long long> ctr;
+  uint64_t ntasks = 0, ncap = 0;
+};
+
+// passes B and C over a batch whose node references are complete.  Synchronous: the two totals size the scratch.
+static int correct_walks(mcx_graph *g, const CrView &x, CrWork &w)
+{
+  hipStream_t st = g->stream;
+  const uint64_t n = x.nreads;
+  DevBuf<uint64_t> ntask, ncap;
+  HIP_TRY(ntask.alloc(n + 1));
+  HIP_TRY(ncap.alloc(n + 1));
+  HIP_TRY(w.toff.alloc(n + 1));
+  HIP_TRY(w.coff.alloc(n + 1));
+  HIP_TRY(w.ctr.alloc(kCrAllCounters));
+  HIP_TRY(hipMemsetAsync(w.ctr.p, 0, kCrAllCounters * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(ntask.p + n, 0, 8, st));
+  HIP_TRY(hipMemsetAsync(ncap.p + n, 0, 8, st));
+  GRID_LAUNCH(k_cr_tasks<false>, n * 64, x, g->t, ntask.p, ncap.p, (const uint64_t *)nullptr, (const uint64_t *)nullptr, (CrTask *)nullptr,
+              (unsigned long long *)nullptr);
+  int rc;
+  if ((rc = device_scan(st, (const uint64_t *)ntask.p, w.toff.p, n + 1)) != MCX_OK) return rc;
+  if ((rc = device_scan(st, (const uint64_t *)ncap.p, w.coff.p, n + 1)) != MCX_OK) return rc;
+  HIP_TRY(hipMemcpy(&w.ntasks, w.toff.p + n, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&w.ncap, w.coff.p + n, 8, hipMemcpyDeviceToHost));
+  ntask.release();
+  ncap.release();
+  HIP_TRY(w.tasks.alloc(std::max<uint64_t>(w.ntasks, 1)));
+  HIP_TRY(w.res.alloc(std::max<uint64_t>(w.ntasks, 1)));
+  HIP_TRY(w.refs.alloc(std::max<uint64_t>(w.ncap, 1)));
+  HIP_TRY(w.codes.alloc(std::max<uint64_t>(w.ncap, 1)));
+  GRID_LAUNCH(k_cr_tasks<true>, n * 64, x, g->t, (uint64_t *)nullptr, (uint64_t *)nullptr, (const uint64_t *)w.toff.p, (const uint64_t *)w.coff.p,
+              w.tasks.p, w.ctr.p);
+  if (w.ntasks)
+    GRID_LAUNCH_W(k_cr_walk, w.ntasks * 4, g->t, g->k, (uint32_t)g->ncols, x.colour, x.flags, (const CrTask *)w.tasks.p, w.ntasks, w.refs.p, w.codes.p,
+                  w.res.p, w.ctr.p);
+  return MCX_OK;
+}
+
+static void correct_add_stats(mcx_graph *g, mcx_correct_stats *s, uint64_t nreads, const unsigned long long cnt[2], const unsigned long long *ctr)
+{
+  g->cr_walk_steps = ctr[kCrSteps];
+  if (!s) return;
+  s->num_reads += nreads;
+  s->num_kmers += cnt[0];
+  s->num_kmers_found += cnt[1];
+  uint64_t *f = &s->num_perfect;  // the counters follow in the order of kCrPerfect ..
+  for (uint32_t i = 0; i < kCrNumCounters; i++) f[i] += ctr[i];
+}
+
+extern "C" int mcx_graph_correct_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nbytes, const void *d_stream_off, uint64_t nreads,
+                                            const mcx_correct_params *p, void *d_node, uint64_t pitch, void *d_len, mcx_correct_stats *stats_accum)
+{
+  mcx_correct_params q;
+  int rc = correct_begin(g, p, &q);
+  if (rc != MCX_OK) return rc;
+  if (((uintptr_t)d_stream & 15) != 0 || ((uintptr_t)d_node & 15) != 0) return fail(MCX_ERR_ARG, "correct: the stream and the node array must be 16-byte aligned");
+  if (((uintptr_t)d_stream_off & 7) != 0 || ((uintptr_t)d_len & 7) != 0) return fail(MCX_ERR_ARG, "stream offsets must be 8-byte aligned");
+  if (!nreads) return MCX_OK;
+  if (!d_stream || !d_stream_off || !d_node || !d_len) return fail(MCX_ERR_ARG, "null stream buffers");
+  if ((pitch & 63) != 0 || pitch < nbytes) return fail(MCX_ERR_ARG, "correct: the pitch (%llu) must be a multiple of 64 and hold the stream's %llu positions",
+                                                        (unsigned long long)pitch, (unsigned long long)nbytes);
+  hipStream_t st = g->stream;
+  HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
+  if ((rc = correct_probe(g, (const uint8_t *)d_stream, nbytes, q.colour, (uint64_t *)d_node, pitch)) != MCX_OK) return rc;
+  // the reads' offsets are stream positions and the stream starts at position 0: boff[0] is taken off every position, so
+  // the view's arrays start where read 0 does
+  uint64_t first = 0;
+  HIP_TRY(hipMemcpyAsync(&first, d_stream_off, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (first >= pitch) return fail(MCX_ERR_ARG, "correct: the stream offsets do not describe the stream");
+  const CrView x{(const uint64_t *)d_stream_off, nreads, 1, g->k, (const uint64_t *)d_node + first, (const uint8_t *)d_stream + first, nullptr,
+                 (uint32_t)g->ncols, q.colour, q.flags, q.gap_variance, q.gap_wiggle, (uint8_t)q.fq_zero};
+  CrWork w;
+  auto run = [&]() -> int {
+    int rc2 = correct_walks(g, x, w);
+    if (rc2 != MCX_OK) return rc2;
+    GRID_LAUNCH(k_cr_len, nreads * 64, x, (const CrTask *)w.tasks.p, (const CrRes *)w.res.p, (const uint64_t *)w.toff.p, (uint64_t *)d_len, w.ctr.p);
+    unsigned long long cnt[2], ctr[kCrAllCounters];
+    HIP_TRY(hipMemcpyAsync(cnt, g->d_rt_cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    correct_add_stats(g, stats_accum, nreads, cnt, ctr);
+    return MCX_OK;
+  };
+  rc = run();
+  if (rc != MCX_OK) (void)hipStreamSynchronize(st);  // before the scratch goes
+  return rc;
+}
+
+extern "C" uint64_t mcx_graph_correct_walk_steps(const mcx_graph *g) { return g ? g->cr_walk_steps : 0; }
+
+// Host reads through the pinned staging buffers as ASCII in the stand-alone chunks of mcx_chunk.h, as coverage_batch
+// takes them: a chunk is probed into scratch references indexed by its stream position and placed from there into the
+// batch's, so a read cut into pieces is whole before its tasks are made.  Synchronous.
+extern "C" int mcx_graph_correct(mcx_graph *g, const uint8_t *bases, const uint8_t *quals, const uint64_t *off, uint64_t nreads,
+                                 const mcx_correct_params *p, mcx_sink_fn sink, void *ctx, uint64_t *out_off, mcx_correct_stats *stats_accum)
+{
+  mcx_correct_params q;
+  int rc = correct_begin(g, p, &q);
+  if (rc != MCX_OK) return rc;
+  if (!nreads) { if (out_off) out_off[0] = 0; return MCX_OK; }
+  if (!off || !sink) return fail(MCX_ERR_ARG, "null read buffers");
+  if (!bases && off[nreads] != off[0]) return fail(MCX_ERR_ARG, "null read buffers");
+  if ((rc = ensure_stage(g)) != MCX_OK) return rc;
+  hipStream_t st = g->stream;
+  const uint64_t nbases = off[nreads] - off[0], pitch = std::max<uint64_t>(64, (nbases + 63) / 64 * 64);
+  // layout of a staging buffer: [0, C) stream | offsets (R + 1); R = C / 16 reads at most
+  ChunkLayout lay;
+  if ((rc = alone_layout(g, "correct", 1024, 64, 2, 3, &lay)) != MCX_OK) return rc;
+  const uint64_t C = lay.cap, R = lay.max_reads, off_at = C, spitch = C;
+  if (off_at + 8 * (R + 1) > g->stage_alloc) return fail(MCX_ERR_HIP, "correct: internal error in the staging layout");
+  DevBuf<uint64_t> node, snode, boff, len, ooff;
+  DevBuf<uint8_t> seq, qual, text;
+  CrWork w;
+  unsigned long long cnt[2] = {0, 0}, ctr[kCrAllCounters];
+  uint64_t total = 0;
+  auto run = [&]() -> int {
+    HIP_TRY(node.alloc(pitch));
+    HIP_TRY(snode.alloc(spitch));
+    HIP_TRY(boff.alloc(nreads + 1));
+    HIP_TRY(seq.alloc(pitch));
+    if (quals) HIP_TRY(qual.alloc(pitch));
+    HIP_TRY(hipMemsetAsync(node.p, 0xff, 8 * pitch, st));
+    HIP_TRY(hipMemcpyAsync(boff.p, off, 8 * (nreads + 1), hipMemcpyHostToDevice, st));
+    if (nbases) HIP_TRY(hipMemcpyAsync(seq.p, bases + off[0], nbases, hipMemcpyHostToDevice, st));
+    if (nbases && quals) HIP_TRY(hipMemcpyAsync(qual.p, quals + off[0], nbases, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
+    ReadChunker ck(bases, off, nreads);
+    while (!ck.done()) {
+      int b;
+      int rc2 = next_stage(g, &b);
+      if (rc2 != MCX_OK) return rc2;
+      uint8_t *hs = g->h_stage[b];
+      uint64_t *ho = reinterpret_cast<uint64_t *>(hs + off_at);
+      const Chunk c = ck.fill(lay, hs, ho);
+      const uint64_t own = c.piece_of >= 0 && !c.ended ? c.take - lay.overlap : ~0ull;  // (whole reads and last pieces own all of their own)
+      uint8_t *ds = g->d_stage[b];
+      HIP_TRY(hipMemcpyAsync(ds, hs, c.L, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(ds + off_at, ho, 8 * (c.n + 1), hipMemcpyHostToDevice, st));
+      if ((rc2 = correct_probe(g, ds, c.L, q.colour, snode.p, spitch)) != MCX_OK) return rc2;
+      GRID_LAUNCH(k_cr_place, c.L, reinterpret_cast<const uint64_t *>(ds + off_at), c.n, (const uint64_t *)boff.p, c.r0, c.shift, own,
+                  (const uint64_t *)snode.p, spitch, node.p, pitch);
+      HIP_TRY(hipEventRecord(g->ev[b], st));
+    }
+    snode.release();  // (hipFree waits for the work that reads it)
+    const CrView x{boff.p, nreads, 0, g->k, node.p, seq.p, quals ? qual.p : nullptr, (uint32_t)g->ncols, q.colour, q.flags,
+                   q.gap_variance, q.gap_wiggle, (uint8_t)q.fq_zero};
+    int rc2 = correct_walks(g, x, w);
+    if (rc2 != MCX_OK) return rc2;
+    HIP_TRY(len.alloc(nreads + 1));
+    HIP_TRY(ooff.alloc(nreads + 1));
+    HIP_TRY(hipMemsetAsync(len.p + nreads, 0, 8, st));
+    GRID_LAUNCH(k_cr_len, nreads * 64, x, (const CrTask *)w.tasks.p, (const CrRes *)w.res.p, (const uint64_t *)w.toff.p, len.p, w.ctr.p);
+    if ((rc2 = device_scan(st, (const uint64_t *)len.p, ooff.p, nreads + 1)) != MCX_OK) return rc2;
+    HIP_TRY(hipMemcpy(&total, ooff.p + nreads, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(text.alloc(std::max<uint64_t>(total, 1)));  // sized by the scan
+    GRID_LAUNCH(k_cr_emit, nreads * 64, x, (const CrTask *)w.tasks.p, (const CrRes *)w.res.p, (const uint8_t *)w.codes.p, (const uint64_t *)w.toff.p,
+                (const uint64_t *)ooff.p, text.p);
+    if (out_off) HIP_TRY(hipMemcpyAsync(out_off, ooff.p, 8 * (nreads + 1), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(cnt, g->d_rt_cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the records are complete, the staging buffers are ours
+    HIP_TRY(hipStreamSynchronize(g->cstream));
+    return MCX_OK;
+  };
+  rc = run();
+  if (rc != MCX_OK) { (void)hipStreamSynchronize(st); return rc; }  // before the scratch goes
+  const uint64_t chunk = std::min<uint64_t>(kStageBytes, g->stage_alloc) & ~15ull;
+  auto fetch = [&](uint64_t c0, int b) -> int {
+    HIP_TRY(hipMemcpyAsync(g->h_stage[b], text.p + c0, std::min(total, c0 + chunk) - c0, hipMemcpyDeviceToHost, g->cstream));
+    HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
+    return MCX_OK;
+  };
+  if ((rc = drain_to_sink(g, total, chunk, fetch, sink, ctx, "correct sink failed")) != MCX_OK) return rc;
+  correct_add_stats(g, stats_accum, nreads, cnt, ctr);
   return MCX_OK;
 }
 

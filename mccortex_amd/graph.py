@@ -26,6 +26,7 @@ SYMBOLS = [
     "mcx_graph_subgraph_begin", "mcx_graph_subgraph_seed_reads", "mcx_graph_subgraph_seed_stream_dev", "mcx_graph_subgraph_finish",
     "mcx_graph_reads_touch", "mcx_graph_reads_touch_stream_dev",
     "mcx_graph_coverage", "mcx_graph_coverage_stream_dev", "mcx_graph_coverage_text",
+    "mcx_graph_correct", "mcx_graph_correct_stream_dev", "mcx_graph_correct_walk_steps",
     "mcx_join_create", "mcx_join_configure", "mcx_join_get_stats", "mcx_join_phases", "mcx_join_buffer", "mcx_join_add_records", "mcx_join_finish", "mcx_join_destroy",
 ]
 
@@ -103,6 +104,22 @@ class CoverageStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class CorrectParams(C.Structure):
+    """mcx_correct_params"""
+    _fields_ = [("colour", C.c_uint32), ("flags", C.c_uint32), ("gap_variance", C.c_float), ("gap_wiggle", C.c_float), ("fq_zero", C.c_char)]
+
+
+class CorrectStats(C.Structure):
+    """mcx_correct_stats"""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "num_reads", "num_kmers", "num_kmers_found", "num_perfect", "num_no_kmers", "gaps", "gaps_filled", "gaps_filled_backward",
+        "gaps_too_short", "gaps_too_long_or_stopped", "stops_fork", "stops_colour", "stops_repeat", "missing_edges", "end_gaps",
+        "end_gaps_extended", "bases_filled")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class UnitigsStats(C.Structure):
     """mcx_unitigs_stats"""
     _fields_ = [(n, C.c_uint64) for n in ("num_unitigs", "num_kmers", "num_bytes", "num_cycles")]
@@ -131,6 +148,7 @@ RECORDS_MUST_EXIST = 1
 INFER_POP, INFER_PRESENCE_COVG = 1, 2
 SUBGRAPH_UNITIGS, SUBGRAPH_INVERT = 1, 2
 COVERAGE_EDGES, COVERAGE_DEGREES = 1, 2
+CORRECT_TWO_WAY = 1
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 
 
@@ -190,6 +208,11 @@ def lib():
     L.mcx_graph_coverage.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(CoverageStats)]
     L.mcx_graph_coverage_stream_dev.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64]
     L.mcx_graph_coverage_text.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, SINK_FN, vp, vp, C.POINTER(CoverageStats)]
+    L.mcx_graph_correct.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(CorrectParams), SINK_FN, vp, vp, C.POINTER(CorrectStats)]
+    L.mcx_graph_correct_stream_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(CorrectParams), vp, C.c_uint64, vp,
+                                               C.POINTER(CorrectStats)]
+    L.mcx_graph_correct_walk_steps.argtypes = [vp]
+    L.mcx_graph_correct_walk_steps.restype = C.c_uint64
     L.mcx_graph_unitigs.argtypes = [vp, C.c_int, C.c_uint32, SINK_FN, vp, C.POINTER(UnitigsStats)]
     L.mcx_graph_unitigs_dev.argtypes = [vp, C.POINTER(UnitigsArrays), C.POINTER(UnitigsStats)]
     L.mcx_graph_infer_edges.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint32, u64p]
@@ -611,6 +634,49 @@ class Graph:
         _check(self.L.mcx_graph_coverage_text(self.h, _ptr(bases), _ptr(offsets), nreads, flags, SINK_FN(sink), None, _ptr(line_off),
                                               C.byref(st)))
         return b"".join(parts), line_off, st
+
+    @staticmethod
+    def _correct_params(colour, two_way, gap_variance, gap_wiggle, fq_zero):
+        z = fq_zero.encode() if isinstance(fq_zero, str) else bytes(fq_zero)
+        return CorrectParams(int(colour), CORRECT_TWO_WAY if two_way else 0, float(gap_variance), float(gap_wiggle), z[:1] or b"\0")
+
+    def correct(self, bases, offsets, quals=None, colour=0, two_way=False, gap_variance=0.1, gap_wiggle=5.0, fq_zero=".", stats=None):
+        """`correct` (ctx_correct.c without link files): (bytes, np.uint64 out_off, CorrectStats).  Record r is
+        out[out_off[r]:out_off[r + 1]]: the corrected sequence of read r and, when `quals` (a byte per base) is given, as
+        many quality bytes behind it, `fq_zero` for every base a walk supplied.  `stats`, if given, is added to."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if quals is not None:
+            quals = np.ascontiguousarray(quals, dtype=np.uint8)
+            if len(quals) < (int(offsets[-1]) if len(offsets) else 0):
+                raise ValueError("quals must hold a byte per base")
+        nreads = max(len(offsets) - 1, 0)
+        out_off = np.zeros(nreads + 1, dtype=np.uint64)
+        parts = []
+
+        def sink(_ctx, ptr, n):
+            parts.append(C.string_at(ptr, n))
+            return 0
+
+        st = stats if stats is not None else CorrectStats()
+        prm = self._correct_params(colour, two_way, gap_variance, gap_wiggle, fq_zero)
+        _check(self.L.mcx_graph_correct(self.h, _ptr(bases), _ptr(quals) if quals is not None else None, _ptr(offsets), nreads, C.byref(prm),
+                                        SINK_FN(sink), None, _ptr(out_off), C.byref(st)))
+        return b"".join(parts), out_off, st
+
+    def correct_stream_dev(self, d_stream, nbytes, d_stream_off, nreads, d_node, pitch, d_len, colour=0, two_way=False, gap_variance=0.1,
+                           gap_wiggle=5.0, stats=None):
+        """the probe, the tasks and the walks of `correct` over a stream in HBM (torch tensors or addresses): d_node is
+        scratch of `pitch` 64-bit words, d_len receives the record lengths; returns the CorrectStats"""
+        st = stats if stats is not None else CorrectStats()
+        prm = self._correct_params(colour, two_way, gap_variance, gap_wiggle, ".")
+        _check(self.L.mcx_graph_correct_stream_dev(self.h, _ptr(d_stream), int(nbytes), _ptr(d_stream_off), int(nreads), C.byref(prm),
+                                                   _ptr(d_node), int(pitch), _ptr(d_len), C.byref(st)))
+        return st
+
+    def correct_walk_steps(self):
+        """walker steps of the last correct / correct_stream_dev call"""
+        return int(self.L.mcx_graph_correct_walk_steps(self.h))
 
     def subgraph(self, seeds, dist=0, invert=False, unitigs=False):
         """`subgraph` (ctx_subgraph.c): keep the k-mers within `dist` edges of the k-mers of `seeds` (a list of str or

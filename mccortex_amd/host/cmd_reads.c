@@ -58,17 +58,8 @@ static struct option longopts[] = {
 /* -x given twice */
 #define ONCE(seen) do { if (seen) print_usage(reads_usage, "%s given twice", cmd); } while (0)
 
-/* one --seq / --seq2 / --seqi (AsyncIOInput + AlignReadsData) */
-typedef struct {
-  int kind; /* '1', '2' or 'i' */
-  seq_in *f1, *f2;
-  char *out_base;
-  seq_out *out;
-  size_t printed;
-} reads_task;
-
 /* asyncio_task_parse: <in>:<O> or <in1>:<in2>:<O>, split on ':' or, when there is none, on ',' */
-static void task_parse(reads_task *t, int c, const char *arg)
+void reads_task_parse(reads_task *t, int c, const char *arg)
 {
   memset(t, 0, sizeof(*t));
   t->kind = c;
@@ -93,30 +84,18 @@ static void task_parse(reads_task *t, int c, const char *arg)
   /* (s stays allocated: out_base points into it) */
 }
 
-/* ---- batches on their way from the reader to the device ---- */
-typedef struct {
-  read_batch b;
-  uint8_t *mate; /* [nreads]: 1 = read i and read i + 1 are a pair */
-  size_t task;
-} work;
+/* ---- batches on their way from the reader to the device (reads_run, host.h) ---- */
+typedef reads_work work;
 
+/* what `reads` does with a batch */
 typedef struct {
-  reads_task *tasks;
-  size_t ntasks;
-  bool want_quals;
-  /* consumer */
   mcx_graph *g;
   bool invert;
   mcx_touch_stats stats;
   size_t total_reads;
   uint8_t *hit;
   size_t cap_hit;
-  /* queue of one batch between the two threads */
-  bool threaded, done;
-  pthread_mutex_t mu;
-  pthread_cond_t cv;
-  work *slot;
-} reads_run;
+} reads_filter;
 
 static work *work_new(reads_run *R, size_t task)
 {
@@ -136,10 +115,11 @@ static void work_free(work *w)
 }
 
 /* filter_reads over one batch: the device says which reads touch the graph, the survivors go out in input order */
-static void process(reads_run *R, work *w)
+static void process(reads_run *run, work *w)
 {
+  reads_filter *R = run->user;
   const size_t n = w->b.nreads;
-  reads_task *t = &R->tasks[w->task];
+  reads_task *t = &run->tasks[w->task];
   if (n > R->cap_hit) {
     R->cap_hit = n * 2;
     R->hit = realloc(R->hit, R->cap_hit);
@@ -163,13 +143,12 @@ static void process(reads_run *R, work *w)
       R->total_reads++;
     }
   }
-  work_free(w);
 }
 
 static void emit(reads_run *R, work *w)
 {
   if (!w->b.nreads) { work_free(w); return; }
-  if (!R->threaded) { process(R, w); return; }
+  if (!R->threaded) { R->process(R, w); work_free(w); return; }
   pthread_mutex_lock(&R->mu);
   while (R->slot) pthread_cond_wait(&R->cv, &R->mu);
   R->slot = w;
@@ -273,6 +252,35 @@ static void *reader_main(void *arg)
   return NULL;
 }
 
+void reads_run_tasks(reads_run *R, unsigned nthreads)
+{
+  R->threaded = nthreads > 1;
+  R->done = false;
+  R->slot = NULL;
+  if (R->threaded) { /* the reader fills batch n + 1 while the device works on batch n and its output is written */
+    pthread_t th;
+    pthread_mutex_init(&R->mu, NULL);
+    pthread_cond_init(&R->cv, NULL);
+    if (pthread_create(&th, NULL, reader_main, R) != 0) die("Cannot start the reader thread");
+    for (;;) {
+      pthread_mutex_lock(&R->mu);
+      while (!R->slot && !R->done) pthread_cond_wait(&R->cv, &R->mu);
+      work *w = R->slot;
+      R->slot = NULL;
+      pthread_cond_broadcast(&R->cv);
+      pthread_mutex_unlock(&R->mu);
+      if (!w) break;
+      R->process(R, w);
+      work_free(w);
+    }
+    pthread_join(th, NULL);
+    pthread_mutex_destroy(&R->mu);
+    pthread_cond_destroy(&R->cv);
+  } else {
+    for (size_t i = 0; i < R->ntasks; i++) produce_task(R, i);
+  }
+}
+
 int ctx_reads(int argc, char **argv)
 {
   cmd_mem_args mem = CMD_MEM_ARGS_INIT;
@@ -303,7 +311,7 @@ int ctx_reads(int argc, char **argv)
       case '1': case '2': case 'i':
         tasks = realloc(tasks, (ntasks + 1) * sizeof(*tasks));
         if (!tasks) die("Out of memory");
-        task_parse(&tasks[ntasks++], c, optarg);
+        reads_task_parse(&tasks[ntasks++], c, optarg);
         break;
       case OPT_DEVICE: if (!parse_entire_uint(optarg, &device)) print_usage(reads_usage, "%s requires an int x >= 0: %s", cmd, optarg); break;
       case ':': case '?': die("`" CMD_NAME " reads -h` for help. Bad option: %s", argv[optind - 1]);
@@ -348,34 +356,16 @@ int ctx_reads(int argc, char **argv)
 
   status("Printing reads that do %stouch the graph\n", invert ? "not " : "");
 
+  reads_filter F;
+  memset(&F, 0, sizeof(F));
+  F.g = g; F.invert = invert;
   reads_run R;
   memset(&R, 0, sizeof(R));
   R.tasks = tasks; R.ntasks = ntasks;
   R.want_quals = fmt == SEQ_FMT_FASTQ;
-  R.g = g; R.invert = invert;
-  R.threaded = nthreads > 1;
-  if (R.threaded) { /* the reader fills batch n + 1 while the device decides batch n and its survivors are written */
-    pthread_t th;
-    pthread_mutex_init(&R.mu, NULL);
-    pthread_cond_init(&R.cv, NULL);
-    if (pthread_create(&th, NULL, reader_main, &R) != 0) die("Cannot start the reader thread");
-    for (;;) {
-      pthread_mutex_lock(&R.mu);
-      while (!R.slot && !R.done) pthread_cond_wait(&R.cv, &R.mu);
-      work *w = R.slot;
-      R.slot = NULL;
-      pthread_cond_broadcast(&R.cv);
-      pthread_mutex_unlock(&R.mu);
-      if (!w) break;
-      process(&R, w);
-    }
-    pthread_join(th, NULL);
-    pthread_mutex_destroy(&R.mu);
-    pthread_cond_destroy(&R.cv);
-  } else {
-    for (size_t i = 0; i < ntasks; i++) produce_task(&R, i);
-  }
-  free(R.hit);
+  R.process = process; R.user = &F;
+  reads_run_tasks(&R, nthreads);
+  free(F.hit);
 
   size_t total_printed = 0;
   for (size_t i = 0; i < ntasks; i++) {
@@ -385,8 +375,8 @@ int ctx_reads(int argc, char **argv)
     if (tasks[i].f2) seq_in_close(tasks[i].f2);
   }
   free(tasks);
-  status("Total printed %zu / %zu (%.2f%%) reads\n", total_printed, R.total_reads,
-         R.total_reads ? (100.0 * (double)total_printed) / (double)R.total_reads : 0.0);
+  status("Total printed %zu / %zu (%.2f%%) reads\n", total_printed, F.total_reads,
+         F.total_reads ? (100.0 * (double)total_printed) / (double)F.total_reads : 0.0);
   mcx_graph_destroy(g);
   return EXIT_SUCCESS;
 }

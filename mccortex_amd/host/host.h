@@ -4,6 +4,7 @@
 #ifndef MCX_HOST_H_
 #define MCX_HOST_H_
 
+#include <pthread.h>
 #include <stdbool.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -198,6 +199,7 @@ int ctx_subgraph(int argc, char **argv);    /* src/commands/ctx_subgraph.c */
 int ctx_unitigs(int argc, char **argv);     /* src/commands/ctx_unitigs.c */
 int ctx_reads(int argc, char **argv);       /* src/commands/ctx_reads.c */
 int ctx_coverage(int argc, char **argv);    /* src/commands/ctx_coverage.c */
+int ctx_correct(int argc, char **argv);     /* src/commands/ctx_correct.c */
 int ctx_join(int argc, char **argv);        /* src/commands/ctx_join.c */
 int ctx_hashtest(int argc, char **argv);    /* src/commands/ctx_exp_hashtest.c */
 
@@ -208,6 +210,42 @@ typedef struct seq_out seq_out;
 seq_out *seq_out_open(const char *out_base, seq_fmt fmt, bool is_pe, bool force);
 /* read i of the batch into the unpaired file (which = 0) or into <O>.1 / <O>.2 (which = 1 / 2) */
 void seq_out_print(seq_out *o, int which, const read_batch *b, size_t i);
+/* the same from parts: the name with `extra` (or NULL) behind it, a sequence of n bases, its qualities (or NULL); a
+ * quality byte of 0, and every one of a sequence without qualities, is written as fq_zero */
+void seq_out_print_parts(seq_out *o, int which, const char *name, size_t nlen, const char *extra, size_t elen, const uint8_t *seq, size_t n,
+                         const uint8_t *qual, char fq_zero);
 void seq_out_close(seq_out *o, bool rm); /* rm: delete the files as well */
+
+/* ---- the batch loop of the commands that take --seq / --seq2 / --seqi tasks (cmd_reads.c): the reads of every task in
+ * order, batch by batch with the pairs marked, handed to `process` in input order; with more than one thread a reader
+ * parses batch n + 1 while batch n is processed (AsyncIOInput + asyncio_run_pool) ---- */
+typedef struct {
+  int kind; /* '1', '2' or 'i' */
+  seq_in *f1, *f2;
+  char *out_base;
+  seq_out *out;
+  size_t printed;
+} reads_task;
+typedef struct {
+  read_batch b;
+  uint8_t *mate; /* [nreads]: 1 = read i and read i + 1 are a pair */
+  size_t task;
+} reads_work;
+typedef struct reads_run reads_run;
+struct reads_run {
+  reads_task *tasks;
+  size_t ntasks;
+  bool want_quals;
+  void (*process)(reads_run *R, reads_work *w); /* the consumer; the batch is freed behind it */
+  void *user;
+  /* queue of one batch between the two threads */
+  bool threaded, done;
+  pthread_mutex_t mu;
+  pthread_cond_t cv;
+  reads_work *slot;
+};
+/* asyncio_task_parse: <in>:<O> or <in1>:<in2>:<O>; opens the inputs, dies on a failure */
+void reads_task_parse(reads_task *t, int c, const char *arg);
+void reads_run_tasks(reads_run *R, unsigned nthreads);
 
 #endif

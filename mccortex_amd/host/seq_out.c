@@ -102,6 +102,30 @@ static void put(seq_out *o, int which, const void *p, size_t n)
   }
 }
 
+void seq_out_print_parts(seq_out *o, int which, const char *name, size_t nlen, const char *extra, size_t elen, const uint8_t *seq, size_t n,
+                         const uint8_t *qual, char fq_zero)
+{
+  if (o->fmt != SEQ_FMT_PLAIN) {
+    put(o, which, o->fmt == SEQ_FMT_FASTQ ? "@" : ">", 1);
+    put(o, which, name, nlen);
+    if (extra) put(o, which, extra, elen);
+    put(o, which, "\n", 1);
+  }
+  put(o, which, seq, n);
+  put(o, which, "\n", 1);
+  if (o->fmt == SEQ_FMT_FASTQ) {
+    if (n + 1 > o->qcap) {
+      o->qcap = (n + 1) * 2;
+      o->qbuf = realloc(o->qbuf, o->qcap);
+      if (!o->qbuf) die("Out of memory");
+    }
+    for (size_t j = 0; j < n; j++) o->qbuf[j] = qual && qual[j] ? (char)qual[j] : fq_zero;
+    o->qbuf[n] = '\n';
+    put(o, which, "+\n", 2);
+    put(o, which, o->qbuf, n + 1);
+  }
+}
+
 void seq_out_print(seq_out *o, int which, const read_batch *b, size_t i)
 {
   const size_t at = (size_t)b->offsets[i], n = (size_t)(b->offsets[i + 1] - b->offsets[i]);
