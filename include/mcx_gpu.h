@@ -576,6 +576,53 @@ int mcx_graph_correct_stream_dev(mcx_graph *g, const void *d_stream, uint64_t nb
  * divides by k_cr_walk's time */
 uint64_t mcx_graph_correct_walk_steps(const mcx_graph *g);
 
+/* `thread` (src/commands/ctx_thread.c without -p and -u; src/tools/generate_paths.c): reads are laid over a graph of ONE
+ * colour and the links of their contigs are generated, counted and kept on the handle.  The walkers hold no paths, so
+ * the links are a function of the graph and the reads alone.  A k-mer is in the sample iff its value word is non-zero;
+ * an edge that names an absent k-mer counts as no edge, so a degree counts the edges whose k-mer is a key.
+ *   Contigs (correct_alignment_nxt:361-510): alignment, segments, gaps and their bounds are those of mcx_graph_correct.
+ *       A contig is a run of segments joined by filled gaps with the walked nodes in between; a missing edge ends it
+ *       without a walk, a failed gap ends it and the next starts behind the gap.  There are no end extensions.  A
+ *       perfectly aligned read is a contig like any other.  Every contig adds nodes + k - 1 to the contig histogram.
+ *   Junctions (worker_contig_to_junctions): forward at i if i + 1 < N and outdegree(n[i]) > 1, its base the last of
+ *       n[i + 1]; reverse at i if i > 0 and indegree(n[i]) > 1, its base the first of n[i - 1].  A contig without a
+ *       junction of each kind adds nothing.
+ *   Links (_juncs_to_paths): per reverse junction at i, if a forward junction lies at i or behind it, a link on n[i - 1]
+ *       with the bases of the forward junctions from i - 1 on; per forward junction at i, if a reverse junction lies at i
+ *       or before it, a link on reverse(n[i + 1]) with the complements of the reverse bases from i + 1 downwards.  A link
+ *       is cut to its first max_juncs bases (0: 32767, GPATH_MAX_JUNCS); every generated link counts once, a count stays
+ *       at 255.  Links are equal iff k-mer, orientation, length and bases are.
+ * mcx_graph_thread takes the layout of mcx_graph_add_reads, flushes pending inserts first and is synchronous; the reads
+ * go through the "reads_chunk" pieces of mcx_graph_correct.  MCX_ERR_NOMEM when a batch does not fit.  The links kept
+ * depend on the table's contents, the reads and the parameters alone, not on the table's size, the chunking, the "grid"
+ * knob or how the reads are split over calls.  nreads == 0 is MCX_OK.  Stats: `aln` as mcx_graph_correct counts it
+ * without the end extensions (end_gaps, end_gaps_extended and bases_filled stay 0, stops_* count the gap walks);
+ * contig_kmers = nodes of all contigs; juncs_* = junctions of all contigs; links_added = links generated, equal ones
+ * counted every time.
+ * mcx_graph_links_text writes the .ctp body (gpath_save_sbuf) to `sink` in consecutive ranges: per k-mer `<kmer>
+ * <nlinks>`, then its links in gpath_cmp order (F before R, bases in ACGT order, a prefix before the longer link) as
+ * `<F|R> <njuncs> <nseen> <juncs>` and, with MCX_LINKS_SEQ, ` seq=<bases> juncpos=<i,j,..>` from a walk of gpath_fetch
+ * over the table as it is now.  THE K-MERS COME IN KEY ORDER (the reference writes them in hash-table order).
+ * mcx_graph_links_info: the three totals of the header (path_bytes = sum of (njuncs + 3) / 4).
+ * mcx_graph_links_contig_hist: *n = the distinct contig lengths, the first `cap` of them (ascending) with their counts.
+ * mcx_graph_links_reset forgets links and histogram; mcx_graph_reset does the same.
+ * Refusals (MCX_ERR_ARG): ncols != 1, a graph split over devices, a handle in intersect mode, unknown flags, a negative
+ * or non-finite gap_variance / gap_wiggle, max_juncs > 32767. */
+enum { MCX_THREAD_TWO_WAY = 1 };
+typedef struct { uint32_t flags; float gap_variance /* D, 0.1 */, gap_wiggle /* d, 5 */; uint32_t max_juncs /* 0: 32767 */; } mcx_thread_params;
+typedef struct {
+  mcx_correct_stats aln; /* the fields that apply; the end_* fields and bases_filled stay 0 */
+  uint64_t contigs, contig_kmers, juncs_fw, juncs_rv, links_added;
+} mcx_thread_stats;
+int mcx_graph_thread(mcx_graph *g, const uint8_t *bases, const uint64_t *read_offsets, uint64_t nreads, const mcx_thread_params *p,
+                     mcx_thread_stats *stats_accum /* optional, += */);
+typedef struct { uint64_t num_kmers_with_paths, num_paths, path_bytes; } mcx_links_info;
+int mcx_graph_links_info(mcx_graph *g, mcx_links_info *out);
+int mcx_graph_links_contig_hist(mcx_graph *g, uint64_t *lengths, uint64_t *counts, uint64_t cap, uint64_t *n);
+enum { MCX_LINKS_SEQ = 1 }; /* add seq= and juncpos= */
+int mcx_graph_links_text(mcx_graph *g, uint32_t flags, mcx_sink_fn sink, void *ctx);
+int mcx_graph_links_reset(mcx_graph *g);
+
 /* `inferedges`: infer_kmer_edges (src/tools/infer_edges.c) for every record of `recs` (.ctx body
  * layout, ncols == the graph's colours) against the k-mers loaded into the graph.  Each edge that some
  * colour lacks (default, --all) or that some colour has and another lacks (MCX_INFER_POP, --pop)

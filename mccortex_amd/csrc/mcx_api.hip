@@ -36,6 +36,7 @@
 #include "mcx_reads.h"
 #include "mcx_coverage.h"
 #include "mcx_correct.h"
+#include "mcx_thread.h"
 #include "mcx_chunk.h"
 
 using namespace mcx;
@@ -308,6 +309,7 @@ struct mcx_graph {
   uint64_t *d_rt_mask = nullptr;           // hit masks of the device entry, 1 bit per stream position (grows, never shrinks)
   uint64_t rt_mask_bytes = 0;
   uint64_t cr_walk_steps = 0;              // walker steps of the last `correct` call (mcx_graph_correct_walk_steps)
+  struct ThreadStore *links = nullptr;     // thread: the links generated so far and the contig histogram (mcx_thread.h)
   uint64_t reads_chunk = 0;                // test knob: stream bytes per chunk of mcx_graph_reads_touch and of coverage_batch (0 = what a staging buffer holds)
 };
 
@@ -499,6 +501,7 @@ extern "C" int mcx_graph_create_shard(mcx_graph **out, int kmer_size, int ncols,
 
 static void clean_drop(mcx_graph *g);
 static void subgraph_drop(mcx_graph *g);
+static void thread_drop(mcx_graph *g);
 
 extern "C" void mcx_graph_destroy(mcx_graph *g)
 {
@@ -530,6 +533,7 @@ extern "C" void mcx_graph_destroy(mcx_graph *g)
   if (g->d_rt_mask) (void)hipFree(g->d_rt_mask);
   clean_drop(g);
   subgraph_drop(g);
+  thread_drop(g);
   if (g->h_ctr) (void)hipHostFree(g->h_ctr);
   if (g->h_full) (void)hipHostFree(g->h_full);
   if (g->h_snap) {
@@ -551,6 +555,7 @@ extern "C" int mcx_graph_reset(mcx_graph *g)
   HIP_TRY(hipSetDevice(g->device));
   clean_drop(g);
   subgraph_drop(g);
+  thread_drop(g);  // (links name k-mers of the table that goes)
   HIP_TRY(hipMemsetAsync(g->t.rec, 0, g->table_bytes, g->stream));
   HIP_TRY(hipMemsetAsync(touch_base(g), 0, kTouchHdr + g->touch_bytes, g->stream));
   HIP_TRY(hipMemsetAsync(g->d_ctr, 0, sizeof(Counters), g->stream));
@@ -4101,8 +4106,13 @@ struct CrWork {
   uint64_t ntasks = 0, ncap = 0;
 };
 
-// passes B and C over a batch whose node references are complete.  Synchronous: the two totals size the scratch.
-static int correct_walks(mcx_graph *g, const CrView &x, CrWork &w)
+// k_cr_tasks without the end extensions, under the names their profile spans carry
+static constexpr auto k_th_tasks_count = &k_cr_tasks<false, false>;
+static constexpr auto k_th_tasks_write = &k_cr_tasks<true, false>;
+
+// passes B and C over a batch whose node references are complete (ends = false: without the end extensions, for
+// `thread`).  Synchronous: the two totals size the scratch.
+static int correct_walks(mcx_graph *g, const CrView &x, CrWork &w, bool ends = true)
 {
   hipStream_t st = g->stream;
   const uint64_t n = x.nreads;
@@ -4115,8 +4125,12 @@ static int correct_walks(mcx_graph *g, const CrView &x, CrWork &w)
   HIP_TRY(hipMemsetAsync(w.ctr.p, 0, kCrAllCounters * sizeof(unsigned long long), st));
   HIP_TRY(hipMemsetAsync(ntask.p + n, 0, 8, st));
   HIP_TRY(hipMemsetAsync(ncap.p + n, 0, 8, st));
-  GRID_LAUNCH(k_cr_tasks<false>, n * 64, x, g->t, ntask.p, ncap.p, (const uint64_t *)nullptr, (const uint64_t *)nullptr, (CrTask *)nullptr,
-              (unsigned long long *)nullptr);
+  if (ends)
+    GRID_LAUNCH(k_cr_tasks<false>, n * 64, x, g->t, ntask.p, ncap.p, (const uint64_t *)nullptr, (const uint64_t *)nullptr, (CrTask *)nullptr,
+                (unsigned long long *)nullptr);
+  else
+    GRID_LAUNCH(k_th_tasks_count, n * 64, x, g->t, ntask.p, ncap.p, (const uint64_t *)nullptr, (const uint64_t *)nullptr, (CrTask *)nullptr,
+                (unsigned long long *)nullptr);
   int rc;
   if ((rc = device_scan(st, (const uint64_t *)ntask.p, w.toff.p, n + 1)) != MCX_OK) return rc;
   if ((rc = device_scan(st, (const uint64_t *)ncap.p, w.coff.p, n + 1)) != MCX_OK) return rc;
@@ -4128,8 +4142,12 @@ static int correct_walks(mcx_graph *g, const CrView &x, CrWork &w)
   HIP_TRY(w.res.alloc(std::max<uint64_t>(w.ntasks, 1)));
   HIP_TRY(w.refs.alloc(std::max<uint64_t>(w.ncap, 1)));
   HIP_TRY(w.codes.alloc(std::max<uint64_t>(w.ncap, 1)));
-  GRID_LAUNCH(k_cr_tasks<true>, n * 64, x, g->t, (uint64_t *)nullptr, (uint64_t *)nullptr, (const uint64_t *)w.toff.p, (const uint64_t *)w.coff.p,
-              w.tasks.p, w.ctr.p);
+  if (ends)
+    GRID_LAUNCH(k_cr_tasks<true>, n * 64, x, g->t, (uint64_t *)nullptr, (uint64_t *)nullptr, (const uint64_t *)w.toff.p, (const uint64_t *)w.coff.p,
+                w.tasks.p, w.ctr.p);
+  else
+    GRID_LAUNCH(k_th_tasks_write, n * 64, x, g->t, (uint64_t *)nullptr, (uint64_t *)nullptr, (const uint64_t *)w.toff.p, (const uint64_t *)w.coff.p,
+                w.tasks.p, w.ctr.p);
   if (w.ntasks)
     GRID_LAUNCH_W(k_cr_walk, w.ntasks * 4, g->t, g->k, (uint32_t)g->ncols, x.colour, x.flags, (const CrTask *)w.tasks.p, w.ntasks, w.refs.p, w.codes.p,
                   w.res.p, w.ctr.p);
@@ -4273,6 +4291,409 @@ extern "C" int mcx_graph_correct(mcx_graph *g, const uint8_t *bases, const uint8
   };
   if ((rc = drain_to_sink(g, total, chunk, fetch, sink, ctx, "correct sink failed")) != MCX_OK) return rc;
   correct_add_stats(g, stats_accum, nreads, cnt, ctr);
+  return MCX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// thread (ctx_thread.c): the links of reads laid over the graph -- mcx_thread.h
+// ---------------------------------------------------------------------------
+// A sorted run of unique links with the pool that holds their bases.
+struct ThSegment {
+  ThLink *links = nullptr;
+  uint64_t *pool = nullptr;
+  uint64_t n = 0;
+  uint32_t maxlen = 0;
+};
+// seg[0]: the merged links; behind it what the calls since the last merge have added.  hist[n] = contigs of n nodes.
+struct ThreadStore {
+  std::vector<ThSegment> seg;
+  unsigned long long *hist = nullptr;
+  uint64_t hist_cap = 0;
+};
+
+static void th_free(ThSegment &s)
+{
+  if (s.links) (void)hipFree(s.links);
+  if (s.pool) (void)hipFree(s.pool);
+  s = ThSegment();
+}
+
+static void thread_drop(mcx_graph *g)
+{
+  if (!g->links) return;
+  for (auto &s : g->links->seg) th_free(s);
+  if (g->links->hist) (void)hipFree(g->links->hist);
+  delete g->links;
+  g->links = nullptr;
+}
+
+// pass G: the m links of `in`, of which nvalid are links at all, sorted; equal ones made one.  Synchronous.
+static int th_sort_reduce(mcx_graph *g, const ThLink *in, uint64_t m, uint64_t nvalid, uint32_t maxlen, ThSegment *out)
+{
+  hipStream_t st = g->stream;
+  *out = ThSegment();
+  if (!nvalid) return MCX_OK;
+  const uint32_t W = (uint32_t)g->W, nj = (maxlen + 31u) / 32u;
+  DevBuf<uint64_t> k0, k1, p0, p1, ex, runstart, nwords, woff;
+  DevBuf<uint8_t> tmp, head;
+  HIP_TRY(k0.alloc(m));
+  HIP_TRY(k1.alloc(m));
+  HIP_TRY(p0.alloc(m));
+  HIP_TRY(p1.alloc(m));
+  hipLaunchKernelGGL(k_iota, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, p0.p, m);
+  HIP_TRY(hipGetLastError());
+  size_t tmp_bytes = 0;
+  int rc = sort_perm_scratch(st, m, &tmp_bytes);
+  if (rc != MCX_OK) return rc;
+  HIP_TRY(tmp.alloc(tmp_bytes ? tmp_bytes : 16));
+  auto word = [&](int w, bool, const uint64_t *through, uint64_t *dst, const uint64_t **) -> int {
+    GRID_LAUNCH(k_th_word, m, in, through, (uint32_t)w, W, nj, dst, m);
+    return MCX_OK;
+  };
+  uint64_t *const keys[2] = {k0.p, k1.p}, *const perms[2] = {p0.p, p1.p}, *perm = nullptr;
+  if ((rc = sort_perm_by_words(st, m, (int)(W + nj + 1), 64, keys, perms, tmp.p, tmp_bytes, g, word, &perm)) != MCX_OK) return rc;
+  HIP_TRY(head.alloc(nvalid + 1));
+  HIP_TRY(ex.alloc(nvalid + 1));
+  GRID_LAUNCH(k_th_heads, nvalid + 1, in, (const uint64_t *)perm, nvalid, head.p);
+  if ((rc = device_scan(st, (const uint8_t *)head.p, ex.p, nvalid + 1)) != MCX_OK) return rc;
+  uint64_t nruns = 0, words = 0;
+  HIP_TRY(hipMemcpy(&nruns, ex.p + nvalid, 8, hipMemcpyDeviceToHost));
+  k0.release();
+  k1.release();
+  tmp.release();
+  HIP_TRY(runstart.alloc(nruns + 1));
+  HIP_TRY(nwords.alloc(nruns + 1));
+  HIP_TRY(woff.alloc(nruns + 1));
+  ThSegment s;
+  ScopeExit undo([&] { th_free(s); });
+  HIP_TRY(hipMalloc((void **)&s.links, nruns * sizeof(ThLink)));
+  GRID_LAUNCH(k_th_runs, nvalid + 1, (const uint8_t *)head.p, (const uint64_t *)ex.p, nvalid, runstart.p);
+  GRID_LAUNCH(k_th_reduce, nruns + 1, in, (const uint64_t *)perm, (const uint64_t *)runstart.p, nruns, s.links, nwords.p);
+  if ((rc = device_scan(st, (const uint64_t *)nwords.p, woff.p, nruns + 1)) != MCX_OK) return rc;
+  HIP_TRY(hipMemcpy(&words, woff.p + nruns, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMalloc((void **)&s.pool, (words + 1) * 8));
+  HIP_TRY(hipMemsetAsync(s.pool, 0, (words + 1) * 8, st));
+  GRID_LAUNCH(k_th_copy, nruns, s.links, (const uint64_t *)woff.p, nruns, s.pool);
+  HIP_TRY(hipStreamSynchronize(st));  // before the scratch and the links that were viewed go
+  s.n = nruns;
+  s.maxlen = maxlen;
+  undo.dismiss();
+  *out = s;
+  return MCX_OK;
+}
+
+// The segments made one.  Without `force` only once the pending links outgrow the merged ones: every link is then
+// sorted again only after as many new ones have come, so many small calls cost amortised linear work (times the sort).
+static int th_merge(mcx_graph *g, bool force)
+{
+  ThreadStore *S = g->links;
+  if (!S || S->seg.size() < 2) return MCX_OK;
+  uint64_t pending = 0;
+  uint32_t maxlen = 0;
+  for (size_t i = 1; i < S->seg.size(); i++) pending += S->seg[i].n;
+  if (!force && pending <= S->seg[0].n) return MCX_OK;
+  if (!S->seg[0].n && S->seg.size() == 2) {  // nothing to merge with
+    th_free(S->seg[0]);
+    S->seg.erase(S->seg.begin());
+    return MCX_OK;
+  }
+  hipStream_t st = g->stream;
+  const uint64_t m = pending + S->seg[0].n;
+  DevBuf<ThLink> all;
+  HIP_TRY(all.alloc(std::max<uint64_t>(m, 1)));
+  uint64_t at = 0;
+  for (auto &s : S->seg) {  // (the links keep pointing into their segments' pools)
+    if (s.n) HIP_TRY(hipMemcpyAsync(all.p + at, s.links, s.n * sizeof(ThLink), hipMemcpyDeviceToDevice, st));
+    at += s.n;
+    maxlen = std::max(maxlen, s.maxlen);
+  }
+  ThSegment merged;
+  int rc = th_sort_reduce(g, all.p, m, m, maxlen, &merged);
+  if (rc != MCX_OK) { (void)hipStreamSynchronize(st); return rc; }
+  for (auto &s : S->seg) th_free(s);
+  S->seg.assign(1, merged);
+  return MCX_OK;
+}
+
+static int thread_begin(mcx_graph *g, const mcx_thread_params *p, uint32_t *max_juncs)
+{
+  int rc = lookup_begin(g, "thread");
+  if (rc != MCX_OK) return rc;
+  if (!p) return fail(MCX_ERR_ARG, "thread: null parameters");
+  if (g->ncols != 1) return fail(MCX_ERR_ARG, "thread: links are made over a graph of one colour, this one has %d", g->ncols);
+  if (p->flags & ~(uint32_t)MCX_THREAD_TWO_WAY) return fail(MCX_ERR_ARG, "thread: unknown flags 0x%x", p->flags);
+  if (!std::isfinite(p->gap_variance) || !std::isfinite(p->gap_wiggle) || p->gap_variance < 0 || p->gap_wiggle < 0)
+    return fail(MCX_ERR_ARG, "thread: the gap variance and the gap wiggle must be finite and not negative");
+  if (p->max_juncs > kThMaxJuncs) return fail(MCX_ERR_ARG, "thread: a link holds %u junctions at the most (max_juncs = %u)", kThMaxJuncs, p->max_juncs);
+  *max_juncs = p->max_juncs ? p->max_juncs : kThMaxJuncs;
+  if (!g->links) {
+    g->links = new ThreadStore();
+    g->links->seg.push_back(ThSegment());
+  }
+  return MCX_OK;
+}
+
+// passes D-G over a batch whose walks are done; tc = the counters of mcx_thread.h on the host
+static int thread_links(mcx_graph *g, const CrView &x, const CrWork &w, uint32_t max_juncs, unsigned long long *tc)
+{
+  hipStream_t st = g->stream;
+  ThreadStore *S = g->links;
+  const uint64_t nreads = x.nreads;
+  DevBuf<unsigned long long> d_tc, pf, pr;
+  DevBuf<uint64_t> nnode, noff, cn, cs, cend, fwx, rvx;
+  DevBuf<uint8_t> fwf, rvf, fwb, rvb;
+  DevBuf<ThLink> links;
+  int rc;
+  HIP_TRY(d_tc.alloc(kThAllCounters));
+  HIP_TRY(hipMemsetAsync(d_tc.p, 0, kThAllCounters * sizeof(unsigned long long), st));
+  HIP_TRY(nnode.alloc(nreads + 1));
+  HIP_TRY(noff.alloc(nreads + 1));
+  HIP_TRY(hipMemsetAsync(nnode.p + nreads, 0, 8, st));
+  GRID_LAUNCH(k_th_nodes<false>, nreads * 64, x, g->t, (const CrTask *)w.tasks.p, (const CrRes *)w.res.p, (const uint64_t *)w.refs.p,
+              (const uint64_t *)w.toff.p, (const uint64_t *)nullptr, nnode.p, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr,
+              (unsigned long long *)nullptr, d_tc.p);
+  if ((rc = device_scan(st, (const uint64_t *)nnode.p, noff.p, nreads + 1)) != MCX_OK) return rc;
+  uint64_t nn = 0;
+  HIP_TRY(hipMemcpy(&nn, noff.p + nreads, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tc, d_tc.p, kThAllCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (!nn) return MCX_OK;
+  if (tc[kThMaxNodes] + 1 > S->hist_cap) {  // the histogram grows to the longest contig there can be
+    const uint64_t cap = std::max<uint64_t>(2 * S->hist_cap, tc[kThMaxNodes] + 1);
+    unsigned long long *h = nullptr;
+    HIP_TRY(hipMalloc((void **)&h, cap * 8));
+    if (hipMemsetAsync(h, 0, cap * 8, st) != hipSuccess ||
+        (S->hist_cap && hipMemcpyAsync(h, S->hist, S->hist_cap * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) || hipStreamSynchronize(st) != hipSuccess) {
+      (void)hipFree(h);
+      return fail(MCX_ERR_HIP, "thread: the contig histogram could not grow");
+    }
+    if (S->hist) (void)hipFree(S->hist);
+    S->hist = h;
+    S->hist_cap = cap;
+  }
+  nnode.release();
+  HIP_TRY(cn.alloc(nn));
+  HIP_TRY(cs.alloc(nn));
+  HIP_TRY(cend.alloc(nn));
+  GRID_LAUNCH(k_th_nodes<true>, nreads * 64, x, g->t, (const CrTask *)w.tasks.p, (const CrRes *)w.res.p, (const uint64_t *)w.refs.p,
+              (const uint64_t *)w.toff.p, (const uint64_t *)noff.p, (uint64_t *)nullptr, cn.p, cs.p, cend.p, S->hist, d_tc.p);
+  HIP_TRY(fwf.alloc(nn + 1));
+  HIP_TRY(rvf.alloc(nn + 1));
+  HIP_TRY(fwb.alloc(nn));
+  HIP_TRY(rvb.alloc(nn));
+  HIP_TRY(fwx.alloc(nn + 1));
+  HIP_TRY(rvx.alloc(nn + 1));
+  HIP_TRY(hipMemsetAsync(fwf.p + nn, 0, 1, st));
+  HIP_TRY(hipMemsetAsync(rvf.p + nn, 0, 1, st));
+  GRID_LAUNCH_W(k_th_junc, nn, g->t, g->k, (const uint64_t *)cn.p, (const uint64_t *)cs.p, (const uint64_t *)cend.p, nn, fwf.p, rvf.p, fwb.p, rvb.p, d_tc.p);
+  if ((rc = device_scan(st, (const uint8_t *)fwf.p, fwx.p, nn + 1)) != MCX_OK) return rc;
+  if ((rc = device_scan(st, (const uint8_t *)rvf.p, rvx.p, nn + 1)) != MCX_OK) return rc;
+  uint64_t nfw = 0, nrv = 0;
+  HIP_TRY(hipMemcpy(&nfw, fwx.p + nn, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&nrv, rvx.p + nn, 8, hipMemcpyDeviceToHost));
+  if (nfw && nrv) {
+    const uint64_t wf = nfw / 32 + 2, wr = nrv / 32 + 2;
+    HIP_TRY(pf.alloc(wf));
+    HIP_TRY(pr.alloc(wr));
+    HIP_TRY(links.alloc(nfw + nrv));
+    HIP_TRY(hipMemsetAsync(pf.p, 0, wf * 8, st));
+    HIP_TRY(hipMemsetAsync(pr.p, 0, wr * 8, st));
+    GRID_LAUNCH(k_th_pack, nn, (const uint8_t *)fwf.p, (const uint8_t *)rvf.p, (const uint8_t *)fwb.p, (const uint8_t *)rvb.p, (const uint64_t *)fwx.p,
+                (const uint64_t *)rvx.p, nn, pf.p, pr.p);
+    GRID_LAUNCH_W(k_th_links, nn, g->t, (const uint64_t *)cn.p, (const uint64_t *)cs.p, (const uint64_t *)cend.p, (const uint8_t *)fwf.p,
+                  (const uint8_t *)rvf.p, (const uint64_t *)fwx.p, (const uint64_t *)rvx.p, nn, max_juncs, reinterpret_cast<const uint64_t *>(pf.p),
+                  reinterpret_cast<const uint64_t *>(pr.p), links.p, d_tc.p);
+  }
+  HIP_TRY(hipMemcpyAsync(tc, d_tc.p, kThAllCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (!tc[kThLinks]) return MCX_OK;
+  ThSegment seg;
+  if ((rc = th_sort_reduce(g, links.p, nfw + nrv, tc[kThLinks], (uint32_t)tc[kThMaxLen], &seg)) != MCX_OK) return rc;
+  S->seg.push_back(seg);
+  return th_merge(g, false);
+}
+
+// Host reads in the chunks of mcx_graph_correct; passes A-C are its own, without the end extensions.  Synchronous.
+extern "C" int mcx_graph_thread(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, const mcx_thread_params *p,
+                                mcx_thread_stats *stats_accum)
+{
+  uint32_t max_juncs = 0;
+  int rc = thread_begin(g, p, &max_juncs);
+  if (rc != MCX_OK) return rc;
+  if (!nreads) return MCX_OK;
+  if (!off) return fail(MCX_ERR_ARG, "null read buffers");
+  if (!bases && off[nreads] != off[0]) return fail(MCX_ERR_ARG, "null read buffers");
+  if ((rc = ensure_stage(g)) != MCX_OK) return rc;
+  hipStream_t st = g->stream;
+  const uint64_t nbases = off[nreads] - off[0], pitch = std::max<uint64_t>(64, (nbases + 63) / 64 * 64);
+  ChunkLayout lay;
+  if ((rc = alone_layout(g, "thread", 1024, 64, 2, 3, &lay)) != MCX_OK) return rc;
+  const uint64_t C = lay.cap, R = lay.max_reads, off_at = C, spitch = C;
+  if (off_at + 8 * (R + 1) > g->stage_alloc) return fail(MCX_ERR_HIP, "thread: internal error in the staging layout");
+  DevBuf<uint64_t> node, snode, boff;
+  DevBuf<uint8_t> seq;
+  CrWork w;
+  unsigned long long cnt[2] = {0, 0}, ctr[kCrAllCounters], tc[kThAllCounters] = {0};
+  auto run = [&]() -> int {
+    HIP_TRY(node.alloc(pitch));
+    HIP_TRY(snode.alloc(spitch));
+    HIP_TRY(boff.alloc(nreads + 1));
+    HIP_TRY(seq.alloc(pitch));
+    HIP_TRY(hipMemsetAsync(node.p, 0xff, 8 * pitch, st));
+    HIP_TRY(hipMemcpyAsync(boff.p, off, 8 * (nreads + 1), hipMemcpyHostToDevice, st));
+    if (nbases) HIP_TRY(hipMemcpyAsync(seq.p, bases + off[0], nbases, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
+    ReadChunker ck(bases, off, nreads);
+    while (!ck.done()) {
+      int b;
+      int rc2 = next_stage(g, &b);
+      if (rc2 != MCX_OK) return rc2;
+      uint8_t *hs = g->h_stage[b];
+      uint64_t *ho = reinterpret_cast<uint64_t *>(hs + off_at);
+      const Chunk c = ck.fill(lay, hs, ho);
+      const uint64_t own = c.piece_of >= 0 && !c.ended ? c.take - lay.overlap : ~0ull;  // (whole reads and last pieces own all of their own)
+      uint8_t *ds = g->d_stage[b];
+      HIP_TRY(hipMemcpyAsync(ds, hs, c.L, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(ds + off_at, ho, 8 * (c.n + 1), hipMemcpyHostToDevice, st));
+      if ((rc2 = correct_probe(g, ds, c.L, 0, snode.p, spitch)) != MCX_OK) return rc2;
+      GRID_LAUNCH(k_cr_place, c.L, reinterpret_cast<const uint64_t *>(ds + off_at), c.n, (const uint64_t *)boff.p, c.r0, c.shift, own,
+                  (const uint64_t *)snode.p, spitch, node.p, pitch);
+      HIP_TRY(hipEventRecord(g->ev[b], st));
+    }
+    snode.release();  // (hipFree waits for the work that reads it)
+    const CrView x{boff.p, nreads, 0, g->k, node.p, seq.p, nullptr, 1u, 0u, (p->flags & MCX_THREAD_TWO_WAY) ? kCrTwoWay : 0u,
+                   p->gap_variance, p->gap_wiggle, (uint8_t)'.'};
+    int rc2 = correct_walks(g, x, w, false);
+    if (rc2 != MCX_OK) return rc2;
+    HIP_TRY(hipMemcpyAsync(cnt, g->d_rt_cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, st));
+    if ((rc2 = thread_links(g, x, w, max_juncs, tc)) != MCX_OK) return rc2;
+    HIP_TRY(hipStreamSynchronize(st));
+    return MCX_OK;
+  };
+  rc = run();
+  if (rc != MCX_OK) { (void)hipStreamSynchronize(st); return rc; }  // before the scratch goes
+  if (stats_accum) {
+    correct_add_stats(g, &stats_accum->aln, nreads, cnt, ctr);
+    stats_accum->contigs += tc[kThContigs];
+    stats_accum->contig_kmers += tc[kThContigKmers];
+    stats_accum->juncs_fw += tc[kThJuncsFw];
+    stats_accum->juncs_rv += tc[kThJuncsRv];
+    stats_accum->links_added += tc[kThLinks];
+  }
+  return MCX_OK;
+}
+
+// what the readers below share: the refusals of `thread`, and the links merged into one sorted segment
+static int links_begin(mcx_graph *g, const ThSegment **seg)
+{
+  static const ThSegment none;
+  int rc = whole_table_only(g, "thread", " (links are made on one device)");
+  if (rc != MCX_OK) return rc;
+  HIP_TRY(hipSetDevice(g->device));
+  *seg = &none;
+  if (!g->links) return MCX_OK;
+  if ((rc = th_merge(g, true)) != MCX_OK) return rc;
+  *seg = &g->links->seg[0];
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_links_info(mcx_graph *g, mcx_links_info *out)
+{
+  const ThSegment *s;
+  int rc = links_begin(g, &s);
+  if (rc != MCX_OK) return rc;
+  if (!out) return fail(MCX_ERR_ARG, "null argument");
+  out->num_kmers_with_paths = out->num_paths = out->path_bytes = 0;
+  if (!s->n) return MCX_OK;
+  hipStream_t st = g->stream;
+  DevBuf<unsigned long long> d;
+  unsigned long long h[2];
+  HIP_TRY(d.alloc(2));
+  HIP_TRY(hipMemsetAsync(d.p, 0, 16, st));
+  GRID_LAUNCH(k_th_info, s->n, (const ThLink *)s->links, s->n, (uint32_t)g->W, d.p);
+  HIP_TRY(hipMemcpyAsync(h, d.p, 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  out->num_kmers_with_paths = h[0];
+  out->num_paths = s->n;
+  out->path_bytes = h[1];
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_links_contig_hist(mcx_graph *g, uint64_t *lengths, uint64_t *counts, uint64_t cap, uint64_t *n)
+{
+  const ThSegment *s;
+  int rc = links_begin(g, &s);
+  if (rc != MCX_OK) return rc;
+  if (!n || (cap && (!lengths || !counts))) return fail(MCX_ERR_ARG, "null argument");
+  *n = 0;
+  if (!g->links || !g->links->hist_cap) return MCX_OK;
+  std::vector<unsigned long long> h(g->links->hist_cap);
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipMemcpy(h.data(), g->links->hist, h.size() * 8, hipMemcpyDeviceToHost));
+  for (uint64_t i = 0; i < h.size(); i++)
+    if (h[i]) {
+      if (*n < cap) { lengths[*n] = i + (uint64_t)g->k - 1; counts[*n] = h[i]; }
+      ++*n;
+    }
+  return MCX_OK;
+}
+
+template <bool EMIT> static int th_text_launch(mcx_graph *g, const ThSegment *s, uint32_t flags, uint64_t *len, const uint64_t *off, uint8_t *out)
+{
+  hipStream_t st = g->stream;
+  SpanGuard sp_(g, EMIT ? "k_th_text<emit>" : "k_th_text<len>");
+  const dim3 grid(cl_grid(g, s->n * 4)), block(256);
+  switch (g->W) {
+    case 1: hipLaunchKernelGGL((k_th_text<1, EMIT>), grid, block, 0, st, g->t, g->k, (const ThLink *)s->links, s->n, flags, len, off, out); break;
+    case 2: hipLaunchKernelGGL((k_th_text<2, EMIT>), grid, block, 0, st, g->t, g->k, (const ThLink *)s->links, s->n, flags, len, off, out); break;
+    case 3: hipLaunchKernelGGL((k_th_text<3, EMIT>), grid, block, 0, st, g->t, g->k, (const ThLink *)s->links, s->n, flags, len, off, out); break;
+    default: hipLaunchKernelGGL((k_th_text<4, EMIT>), grid, block, 0, st, g->t, g->k, (const ThLink *)s->links, s->n, flags, len, off, out); break;
+  }
+  HIP_TRY(hipGetLastError());
+  return MCX_OK;
+}
+
+extern "C" int mcx_graph_links_text(mcx_graph *g, uint32_t flags, mcx_sink_fn sink, void *ctx)
+{
+  const ThSegment *s;
+  int rc = links_begin(g, &s);
+  if (rc != MCX_OK) return rc;
+  if (flags & ~(uint32_t)MCX_LINKS_SEQ) return fail(MCX_ERR_ARG, "links: unknown flags 0x%x", flags);
+  if (!sink) return fail(MCX_ERR_ARG, "null sink");
+  if (!s->n) return MCX_OK;
+  if ((rc = flush_deferred(g)) != MCX_OK) return rc;  // the trace sees every insert made so far
+  if ((rc = ensure_stage(g)) != MCX_OK) return rc;
+  hipStream_t st = g->stream;
+  DevBuf<uint64_t> len, loff;
+  DevBuf<uint8_t> text;
+  uint64_t total = 0;
+  HIP_TRY(len.alloc(s->n + 1));
+  HIP_TRY(loff.alloc(s->n + 1));
+  HIP_TRY(hipMemsetAsync(len.p + s->n, 0, 8, st));
+  if ((rc = th_text_launch<false>(g, s, flags, len.p, nullptr, nullptr)) != MCX_OK) return rc;
+  if ((rc = device_scan(st, (const uint64_t *)len.p, loff.p, s->n + 1)) != MCX_OK) return rc;
+  HIP_TRY(hipMemcpy(&total, loff.p + s->n, 8, hipMemcpyDeviceToHost));
+  len.release();
+  HIP_TRY(text.alloc(std::max<uint64_t>(total, 1)));  // sized by the scan
+  if ((rc = th_text_launch<true>(g, s, flags, nullptr, loff.p, text.p)) != MCX_OK) { (void)hipStreamSynchronize(st); return rc; }
+  HIP_TRY(hipStreamSynchronize(st));  // the text is complete, the staging buffers are ours
+  HIP_TRY(hipStreamSynchronize(g->cstream));
+  const uint64_t chunk = std::min<uint64_t>(kStageBytes, g->stage_alloc) & ~15ull;
+  auto fetch = [&](uint64_t c0, int b) -> int {
+    HIP_TRY(hipMemcpyAsync(g->h_stage[b], text.p + c0, std::min(total, c0 + chunk) - c0, hipMemcpyDeviceToHost, g->cstream));
+    HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
+    return MCX_OK;
+  };
+  return drain_to_sink(g, total, chunk, fetch, sink, ctx, "links sink failed");
+}
+
+extern "C" int mcx_graph_links_reset(mcx_graph *g)
+{
+  int rc = whole_table_only(g, "thread", " (links are made on one device)");
+  if (rc != MCX_OK) return rc;
+  HIP_TRY(hipSetDevice(g->device));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  thread_drop(g);
   return MCX_OK;
 }
 

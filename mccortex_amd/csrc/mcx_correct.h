@@ -150,8 +150,8 @@ __device__ __forceinline__ void cr_bounds(uint64_t est, float D, float d, uint32
 
 // A wave per read.  WRITE = false: ntask[r] and ncap[r]; WRITE = true: the tasks at tasks[toff[r]], their ranges from
 // coff[r] on, and the counters of the alignment.  Task order: the left extension, the gaps in read order, the right
-// extension.
-template <bool WRITE>
+// extension.  ENDS = false (`thread`, mcx_thread.h): the gaps alone, no extension is made a task or counted.
+template <bool WRITE, bool ENDS = true>
 __global__ __launch_bounds__(256) void k_cr_tasks(CrView x, TableView t, uint64_t *ntask, uint64_t *ncap, const uint64_t *toff, const uint64_t *coff,
                                                   CrTask *tasks, unsigned long long *ctr)
 {
@@ -163,6 +163,7 @@ __global__ __launch_bounds__(256) void k_cr_tasks(CrView x, TableView t, uint64_
     const uint64_t nk = len >= k ? len - k + 1 : 0;
     uint64_t nt = 0, nc = 0, prev = 0, prevref = 0, ngaps = 0, nmiss = 0, first = kCrNone;
     auto add = [&](uint32_t kind, uint64_t from, uint64_t to, uint32_t gmin, uint32_t limit, uint32_t cap) {
+      if (!ENDS && kind != kCrGap) return;
       if (WRITE && lane == 0) tasks[toff[r] + nt] = CrTask{from, to, coff[r] + nc, cap, gmin, limit, kind};
       nt++;
       nc += cap;
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256) void k_cr_tasks(CrView x, TableView t, uint64_
     } else if (lane == 0) {
       if (first == kCrNone) c_none++;
       else if (ngaps == 0 && first == 0 && right == 0) { c_perfect++; c_miss += nmiss ? 1 : 0; }  // correct_alignment_init:81-86
-      else { c_miss += nmiss; c_gaps += ngaps; c_end += (first > 0) + (right > 0); }
+      else { c_miss += nmiss; c_gaps += ngaps; c_end += ENDS ? (first > 0) + (right > 0) : 0; }
     }
   }
   if (WRITE) {

@@ -27,6 +27,7 @@ SYMBOLS = [
     "mcx_graph_reads_touch", "mcx_graph_reads_touch_stream_dev",
     "mcx_graph_coverage", "mcx_graph_coverage_stream_dev", "mcx_graph_coverage_text",
     "mcx_graph_correct", "mcx_graph_correct_stream_dev", "mcx_graph_correct_walk_steps",
+    "mcx_graph_thread", "mcx_graph_links_info", "mcx_graph_links_contig_hist", "mcx_graph_links_text", "mcx_graph_links_reset",
     "mcx_join_create", "mcx_join_configure", "mcx_join_get_stats", "mcx_join_phases", "mcx_join_buffer", "mcx_join_add_records", "mcx_join_finish", "mcx_join_destroy",
 ]
 
@@ -120,6 +121,29 @@ class CorrectStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class ThreadParams(C.Structure):
+    """mcx_thread_params"""
+    _fields_ = [("flags", C.c_uint32), ("gap_variance", C.c_float), ("gap_wiggle", C.c_float), ("max_juncs", C.c_uint32)]
+
+
+class ThreadStats(C.Structure):
+    """mcx_thread_stats"""
+    _fields_ = [("aln", CorrectStats)] + [(n, C.c_uint64) for n in ("contigs", "contig_kmers", "juncs_fw", "juncs_rv", "links_added")]
+
+    def as_dict(self):
+        d = self.aln.as_dict()
+        d.update({n: int(getattr(self, n)) for n, _ in self._fields_[1:]})
+        return d
+
+
+class LinksInfo(C.Structure):
+    """mcx_links_info"""
+    _fields_ = [(n, C.c_uint64) for n in ("num_kmers_with_paths", "num_paths", "path_bytes")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class UnitigsStats(C.Structure):
     """mcx_unitigs_stats"""
     _fields_ = [(n, C.c_uint64) for n in ("num_unitigs", "num_kmers", "num_bytes", "num_cycles")]
@@ -149,6 +173,8 @@ INFER_POP, INFER_PRESENCE_COVG = 1, 2
 SUBGRAPH_UNITIGS, SUBGRAPH_INVERT = 1, 2
 COVERAGE_EDGES, COVERAGE_DEGREES = 1, 2
 CORRECT_TWO_WAY = 1
+THREAD_TWO_WAY = 1
+LINKS_SEQ = 1
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 
 
@@ -212,6 +238,11 @@ def lib():
     L.mcx_graph_correct_stream_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(CorrectParams), vp, C.c_uint64, vp,
                                                C.POINTER(CorrectStats)]
     L.mcx_graph_correct_walk_steps.argtypes = [vp]
+    L.mcx_graph_thread.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(ThreadParams), C.POINTER(ThreadStats)]
+    L.mcx_graph_links_info.argtypes = [vp, C.POINTER(LinksInfo)]
+    L.mcx_graph_links_contig_hist.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_graph_links_text.argtypes = [vp, C.c_uint32, SINK_FN, vp]
+    L.mcx_graph_links_reset.argtypes = [vp]
     L.mcx_graph_correct_walk_steps.restype = C.c_uint64
     L.mcx_graph_unitigs.argtypes = [vp, C.c_int, C.c_uint32, SINK_FN, vp, C.POINTER(UnitigsStats)]
     L.mcx_graph_unitigs_dev.argtypes = [vp, C.POINTER(UnitigsArrays), C.POINTER(UnitigsStats)]
@@ -677,6 +708,47 @@ class Graph:
     def correct_walk_steps(self):
         """walker steps of the last correct / correct_stream_dev call"""
         return int(self.L.mcx_graph_correct_walk_steps(self.h))
+
+    def thread(self, bases, offsets, two_way=False, gap_variance=0.1, gap_wiggle=5.0, max_juncs=0, stats=None):
+        """`thread` (ctx_thread.c without -p and -u) over a graph of one colour: the links of the reads' contigs are
+        generated and added to those the handle keeps.  Returns the ThreadStats (`stats`, if given, is added to)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nreads = max(len(offsets) - 1, 0)
+        st = stats if stats is not None else ThreadStats()
+        prm = ThreadParams(THREAD_TWO_WAY if two_way else 0, float(gap_variance), float(gap_wiggle), int(max_juncs))
+        _check(self.L.mcx_graph_thread(self.h, _ptr(bases), _ptr(offsets), nreads, C.byref(prm), C.byref(st)))
+        return st
+
+    def links_info(self):
+        """{num_kmers_with_paths, num_paths, path_bytes} of the links kept"""
+        out = LinksInfo()
+        _check(self.L.mcx_graph_links_info(self.h, C.byref(out)))
+        return out.as_dict()
+
+    def links_contig_hist(self):
+        """[(contig length in bases, contigs)] in ascending length"""
+        n = C.c_uint64(0)
+        _check(self.L.mcx_graph_links_contig_hist(self.h, None, None, 0, C.byref(n)))
+        lengths, counts = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint64)
+        _check(self.L.mcx_graph_links_contig_hist(self.h, _ptr(lengths), _ptr(counts), n.value, C.byref(n)))
+        return list(zip(lengths.tolist(), counts.tolist()))
+
+    def links_text(self, seq=True):
+        """the body of the .ctp file (bytes): per k-mer in key order `<kmer> <nlinks>`, then its links; with `seq` every
+        link carries seq= and juncpos="""
+        parts = []
+
+        def sink(_ctx, ptr, n):
+            parts.append(C.string_at(ptr, n))
+            return 0
+
+        _check(self.L.mcx_graph_links_text(self.h, LINKS_SEQ if seq else 0, SINK_FN(sink), None))
+        return b"".join(parts)
+
+    def links_reset(self):
+        """forget the links and the contig histogram"""
+        _check(self.L.mcx_graph_links_reset(self.h))
 
     def subgraph(self, seeds, dist=0, invert=False, unitigs=False):
         """`subgraph` (ctx_subgraph.c): keep the k-mers within `dist` edges of the k-mers of `seeds` (a list of str or

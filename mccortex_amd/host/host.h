@@ -200,6 +200,7 @@ int ctx_unitigs(int argc, char **argv);     /* src/commands/ctx_unitigs.c */
 int ctx_reads(int argc, char **argv);       /* src/commands/ctx_reads.c */
 int ctx_coverage(int argc, char **argv);    /* src/commands/ctx_coverage.c */
 int ctx_correct(int argc, char **argv);     /* src/commands/ctx_correct.c */
+int ctx_thread(int argc, char **argv);      /* src/commands/ctx_thread.c */
 int ctx_join(int argc, char **argv);        /* src/commands/ctx_join.c */
 int ctx_hashtest(int argc, char **argv);    /* src/commands/ctx_exp_hashtest.c */
 

@@ -1,7 +1,7 @@
 /* mccortex.c -- `mccortex<K> <command>` dispatcher (src/main/mccortex.c:15-28,279-332).
  * `build` (the hot path this repository replaces) and the two commands next to it that run on the
  * same device code: `sort` and `index`, `inferedges` (the step after `build` of every
- * multi-sample pipeline), `clean` (the step after `build` of every pipeline), `popbubbles` (the step after `clean`), `subgraph` (a locus pulled out of the population graph), `unitigs` (the pipeline's last step), `reads` (from a graph back to the reads that touch it), `coverage` (what the graph holds for the k-mers of a sequence), `join` (several samples into one coloured graph), `correct` (reads corrected against the cleaned graph), and the reference's benchmark of this path's table, `hashtest`. */
+ * multi-sample pipeline), `clean` (the step after `build` of every pipeline), `popbubbles` (the step after `clean`), `subgraph` (a locus pulled out of the population graph), `unitigs` (the pipeline's last step), `reads` (from a graph back to the reads that touch it), `coverage` (what the graph holds for the k-mers of a sequence), `join` (several samples into one coloured graph), `correct` (reads corrected against the cleaned graph), `thread` (the links of reads laid over the graph), and the reference's benchmark of this path's table, `hashtest`. */
 #include "host.h"
 
 #include <stdlib.h>
@@ -67,6 +67,7 @@ int main(int argc, char **argv)
   else if (!strcmp(argv[1], "coverage")) func = ctx_coverage; /* (the usage text above and the list below are pinned by recorded transcripts: `coverage -h` has the command's own) */
   else if (!strcmp(argv[1], "join")) func = ctx_join; /* (as `coverage`: not in the pinned texts) */
   else if (!strcmp(argv[1], "correct")) func = ctx_correct; /* (as `coverage`: not in the pinned texts) */
+  else if (!strcmp(argv[1], "thread")) func = ctx_thread; /* (as `coverage`: not in the pinned texts) */
   else if (!strcmp(argv[1], "hashtest")) func = ctx_hashtest;
   if (!func) {
     fprintf(stderr, "%s: command '%s' is not part of this build (build, sort, index, clean, inferedges, popbubbles, subgraph, unitigs, reads and hashtest are)\n\n", CMD_NAME, argv[1]);
