@@ -681,6 +681,14 @@ template <class In> static int device_scan(hipStream_t st, const In *in, uint64_
   HIP_TRY(hipStreamSynchronize(st));  // before tmp goes
   return MCX_OK;
 }
+// ... over counts whose last one is 0, so that out[cnt - 1] is their sum: read back into *total
+template <class In> static int scan_total(hipStream_t st, const In *in, uint64_t *out, uint64_t cnt, uint64_t *total)
+{
+  int rc = device_scan(st, in, out, cnt);
+  if (rc != MCX_OK) return rc;
+  HIP_TRY(hipMemcpy(total, out + cnt - 1, 8, hipMemcpyDeviceToHost));
+  return MCX_OK;
+}
 
 // The multi-word key sort of export, `sort` and unitigs: orders a permutation of m items by W key words with an LSD
 // radix sort, least significant word (W - 1) first, every pass stable.  perm[0] holds the permutation to start from
@@ -2402,6 +2410,21 @@ static int drain_to_sink(mcx_graph *g, uint64_t total, uint64_t chunk, Produce p
   return rc;
 }
 
+// A finished text of `total` bytes on the device (coverage_text, correct, links_text) to a sink, a staging buffer's
+// worth at a time.  Waits for both streams first: the text is complete then, and the staging buffers are the drain's.
+static int text_to_sink(mcx_graph *g, const uint8_t *text, uint64_t total, mcx_sink_fn sink, void *ctx, const char *sink_failed)
+{
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipStreamSynchronize(g->cstream));
+  const uint64_t chunk = std::min<uint64_t>(kStageBytes, g->stage_alloc) & ~15ull;
+  auto fetch = [&](uint64_t c0, int b) -> int {
+    HIP_TRY(hipMemcpyAsync(g->h_stage[b], text + c0, std::min(total, c0 + chunk) - c0, hipMemcpyDeviceToHost, g->cstream));
+    HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
+    return MCX_OK;
+  };
+  return drain_to_sink(g, total, chunk, fetch, sink, ctx, sink_failed);
+}
+
 static int add_reads_qh(mcx_graph *g, int colour, const uint8_t *bases, const uint8_t *quals,
                         const uint64_t *off, uint64_t nreads, uint8_t fq, uint8_t hp);
 static int add_reads_must_exist(mcx_graph *g, int colour, const uint8_t *bases, const uint8_t *quals,
@@ -3832,7 +3855,7 @@ extern "C" int mcx_graph_reads_touch_stream_dev(mcx_graph *g, const void *d_stre
   return reads_touch_launch(g, (const uint8_t *)d_stream, nbytes, (const uint64_t *)d_stream_off, nreads, g->d_rt_mask, (uint8_t *)d_hit);
 }
 
-// The stand-alone chunks (mcx_chunk.h) of `reads` and `coverage` (`what` in the message): a staging buffer is
+// The stand-alone chunks (mcx_chunk.h) of the read commands (`what` in the message): a staging buffer is
 // [0, C) stream | offsets (R + 1) | the command's own regions, R = C / 16 reads at most.  C is what a chunk holds by
 // default or the reads_chunk knob, a multiple of 64 and at least 256, and at most num / den of the buffer less `fixed`
 // bytes: what the command's regions leave.  Buffers of less than min_alloc bytes are refused.
@@ -3845,10 +3868,45 @@ static int alone_layout(const mcx_graph *g, const char *what, uint64_t min_alloc
   *lay = ChunkLayout{0, C, C / 16, (uint64_t)g->k - 1, true};
   return MCX_OK;
 }
+// what the stream and the offsets take of a staging buffer; a command's own regions lie behind them
+static uint64_t alone_bytes(const ChunkLayout &lay) { return lay.cap + 8 * (lay.max_reads + 1); }
 
-// Host reads through the pinned staging buffers as ASCII, in the stand-alone chunks of mcx_chunk.h: every k-mer of a
-// read in pieces starts in exactly one piece, and the read's byte is the OR of its pieces'.
-// One staging pair holds everything of a chunk: stream, offsets, the hit bytes coming back (pinned on the host side)
+// ensure_stage and the layout of the commands that keep nothing of their own in the buffers (coverage, correct, thread)
+static int place_layout(mcx_graph *g, const char *what, ChunkLayout *lay)
+{
+  int rc = ensure_stage(g);
+  if (rc != MCX_OK) return rc;
+  if ((rc = alone_layout(g, what, 1024, 64, 2, 3, lay)) != MCX_OK) return rc;
+  if (alone_bytes(*lay) > g->stage_alloc) return fail(MCX_ERR_HIP, "%s: internal error in the staging layout", what);
+  return MCX_OK;
+}
+
+// Host reads through the pinned staging buffers as ASCII, in the stand-alone chunks of mcx_chunk.h: the staging pairs
+// take turns, a chunk is filled into the host side of one, stream and offsets go up on the handle's stream, and
+// body(b, chunk, d_stream, d_off) enqueues the command's work on pair b behind them and returns an MCX code.  The pair
+// is filled again only after that work is done.  Nothing is synchronised at the end.
+template <class Body>
+static int alone_chunks(mcx_graph *g, const ChunkLayout &lay, const uint8_t *bases, const uint64_t *off, uint64_t nreads, Body body)
+{
+  hipStream_t st = g->stream;
+  const uint64_t off_at = lay.cap;
+  ReadChunker ck(bases, off, nreads);
+  while (!ck.done()) {
+    int b, rc = next_stage(g, &b);
+    if (rc != MCX_OK) return rc;
+    uint8_t *hs = g->h_stage[b], *ds = g->d_stage[b];
+    uint64_t *ho = reinterpret_cast<uint64_t *>(hs + off_at);
+    const Chunk c = ck.fill(lay, hs, ho);
+    HIP_TRY(hipMemcpyAsync(ds, hs, c.L, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ds + off_at, ho, 8 * (c.n + 1), hipMemcpyHostToDevice, st));
+    if ((rc = body(b, c, (const uint8_t *)ds, reinterpret_cast<const uint64_t *>(ds + off_at))) != MCX_OK) return rc;
+    HIP_TRY(hipEventRecord(g->ev[b], st));
+  }
+  return MCX_OK;
+}
+
+// Host reads in alone_chunks: every k-mer of a read in pieces starts in exactly one piece, and the read's byte is the OR
+// of its pieces'.  One staging pair holds everything of a chunk: stream, offsets, the hit bytes coming back (pinned on the host side)
 // and, on the device side only, the hit masks.
 extern "C" int mcx_graph_reads_touch(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, uint8_t *hit,
                                      mcx_touch_stats *stats_accum)
@@ -3862,8 +3920,8 @@ extern "C" int mcx_graph_reads_touch(mcx_graph *g, const uint8_t *bases, const u
   // layout: [0, C) stream | offsets (R + 1) | hit bytes R | masks, 512 bytes per tile; R = C / 16 reads at most
   ChunkLayout lay;
   if ((rc = alone_layout(g, "reads", 704 + 256 * 27 / 16, 704, 16, 27, &lay)) != MCX_OK) return rc;
-  const uint64_t C = lay.cap, R = lay.max_reads, off_at = C, hit_at = (off_at + 8 * (R + 1) + 15) & ~15ull, mask_at = (hit_at + R + 63) & ~63ull;
-  if (mask_at + (C + kTile - 1) / kTile * (kTile / 8) > g->stage_alloc) return fail(MCX_ERR_HIP, "reads: internal error in the staging layout");
+  const uint64_t hit_at = (alone_bytes(lay) + 15) & ~15ull, mask_at = (hit_at + lay.max_reads + 63) & ~63ull;
+  if (mask_at + (lay.cap + kTile - 1) / kTile * (kTile / 8) > g->stage_alloc) return fail(MCX_ERR_HIP, "reads: internal error in the staging layout");
   hipStream_t st = g->stream;
   HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
   memset(hit, 0, nreads);
@@ -3873,25 +3931,17 @@ extern "C" int mcx_graph_reads_touch(mcx_graph *g, const uint8_t *bases, const u
     for (uint64_t j = 0; j < inflight[b].n; j++) hit[inflight[b].r0 + j] |= h[j];
     inflight[b].n = 0;
   };
-  ReadChunker ck(bases, off, nreads);
-  while (!ck.done()) {
-    int b;
-    if ((rc = next_stage(g, &b)) != MCX_OK) return rc;
-    harvest(b);
-    uint8_t *hs = g->h_stage[b];
-    uint64_t *ho = reinterpret_cast<uint64_t *>(hs + off_at);
-    const Chunk c = ck.fill(lay, hs, ho);
-    const uint64_t L = c.L, n = c.n;
+  rc = alone_chunks(g, lay, bases, off, nreads, [&](int b, const Chunk &c, const uint8_t *d_stream, const uint64_t *d_off) -> int {
+    harvest(b);  // (the hit bytes of the pair's last chunk, which filling it has not touched)
     uint8_t *ds = g->d_stage[b];
-    HIP_TRY(hipMemcpyAsync(ds, hs, L, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ds + off_at, ho, 8 * (n + 1), hipMemcpyHostToDevice, st));
-    rc = reads_touch_launch(g, ds, L, reinterpret_cast<const uint64_t *>(ds + off_at), n, reinterpret_cast<uint64_t *>(ds + mask_at), ds + hit_at);
-    if (rc != MCX_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(hs + hit_at, ds + hit_at, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(g->ev[b], st));
+    int rc2 = reads_touch_launch(g, d_stream, c.L, d_off, c.n, reinterpret_cast<uint64_t *>(ds + mask_at), ds + hit_at);
+    if (rc2 != MCX_OK) return rc2;
+    HIP_TRY(hipMemcpyAsync(g->h_stage[b] + hit_at, ds + hit_at, c.n, hipMemcpyDeviceToHost, st));
     inflight[b].r0 = c.r0;
-    inflight[b].n = n;
-  }
+    inflight[b].n = c.n;
+    return MCX_OK;
+  });
+  if (rc != MCX_OK) return rc;
   unsigned long long h[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(h, g->d_rt_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -3942,23 +3992,17 @@ struct CvBatch {
   unsigned long long cnt[2] = {0, 0};
 };
 
-// Host reads through the pinned staging buffers as ASCII, in the stand-alone chunks of mcx_chunk.h: a piece owns the
-// k-mers that start in it, that is all its positions but the last k - 1 (the last piece of a read owns all of its
-// own).  A chunk is probed into scratch arrays indexed by its stream position and placed from there into the
-// batch's.  Synchronous.
+// Host reads in alone_chunks: a piece owns the k-mers that start in it (Chunk::own).  A chunk is probed into scratch
+// arrays indexed by its stream position and placed from there into the batch's.  Synchronous.
 static int coverage_batch(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, bool want_edges, CvBatch &B)
 {
-  int rc = ensure_stage(g);
+  ChunkLayout lay;
+  int rc = place_layout(g, "coverage", &lay);
   if (rc != MCX_OK) return rc;
   hipStream_t st = g->stream;
   const uint64_t ncols = (uint64_t)g->ncols, nbases = off[nreads] - off[0];
   B.pitch = std::max<uint64_t>(64, (nbases + 63) / 64 * 64);
-  // layout of a staging buffer: [0, C) stream | offsets (R + 1); R = C / 16 reads at most
-  ChunkLayout lay;
-  if ((rc = alone_layout(g, "coverage", 1024, 64, 2, 3, &lay)) != MCX_OK) return rc;
-  const uint64_t C = lay.cap, R = lay.max_reads, off_at = C;
-  if (off_at + 8 * (R + 1) > g->stage_alloc) return fail(MCX_ERR_HIP, "coverage: internal error in the staging layout");
-  const uint64_t spitch = C;  // (a multiple of 64)
+  const uint64_t spitch = lay.cap;  // (a multiple of 64)
   DevBuf<uint32_t> scovg;
   DevBuf<uint8_t> sedges;
   HIP_TRY(B.covg.alloc(ncols * B.pitch));
@@ -3968,25 +4012,15 @@ static int coverage_batch(mcx_graph *g, const uint8_t *bases, const uint64_t *of
   if (want_edges) HIP_TRY(sedges.alloc(ncols * spitch));
   HIP_TRY(hipMemcpyAsync(B.off, off, 8 * (nreads + 1), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
-  ReadChunker ck(bases, off, nreads);
   auto run = [&]() -> int {
-    while (!ck.done()) {
-      int b;
-      int rc2 = next_stage(g, &b);
-      if (rc2 != MCX_OK) return rc2;
-      uint8_t *hs = g->h_stage[b];
-      uint64_t *ho = reinterpret_cast<uint64_t *>(hs + off_at);
-      const Chunk c = ck.fill(lay, hs, ho);
-      const uint64_t L = c.L, n = c.n, r0 = c.r0, shift = c.shift;
-      const uint64_t own = c.piece_of >= 0 && !c.ended ? c.take - lay.overlap : ~0ull;  // (whole reads and last pieces own all of their own)
-      uint8_t *ds = g->d_stage[b];
-      HIP_TRY(hipMemcpyAsync(ds, hs, L, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(ds + off_at, ho, 8 * (n + 1), hipMemcpyHostToDevice, st));
-      if ((rc2 = coverage_probe(g, ds, L, scovg, sedges, spitch)) != MCX_OK) return rc2;
-      GRID_LAUNCH(k_cv_place, L, reinterpret_cast<const uint64_t *>(ds + off_at), n, (const uint64_t *)B.off.p, r0, shift, own, (uint32_t)ncols,
-                  (const uint32_t *)scovg.p, (const uint8_t *)sedges.p, spitch, B.covg.p, B.edges.p, B.pitch);
-      HIP_TRY(hipEventRecord(g->ev[b], st));
-    }
+    int rc2 = alone_chunks(g, lay, bases, off, nreads, [&](int, const Chunk &c, const uint8_t *d_stream, const uint64_t *d_off) -> int {
+      int rc3 = coverage_probe(g, d_stream, c.L, scovg, sedges, spitch);
+      if (rc3 != MCX_OK) return rc3;
+      GRID_LAUNCH(k_cv_place, c.L, d_off, c.n, (const uint64_t *)B.off.p, c.r0, c.shift, c.own, (uint32_t)ncols, (const uint32_t *)scovg.p,
+                  (const uint8_t *)sedges.p, spitch, B.covg.p, B.edges.p, B.pitch);
+      return MCX_OK;
+    });
+    if (rc2 != MCX_OK) return rc2;
     HIP_TRY(hipMemcpyAsync(B.cnt, g->d_rt_cnt, sizeof(B.cnt), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return MCX_OK;
@@ -4049,23 +4083,14 @@ extern "C" int mcx_graph_coverage_text(mcx_graph *g, const uint8_t *bases, const
   HIP_TRY(loff.alloc(nlines + 1));
   HIP_TRY(hipMemsetAsync(len.p + nlines, 0, 8, st));
   GRID_LAUNCH(k_cv_len, nreads * (uint64_t)g->ncols, x, len.p);
-  if ((rc = device_scan(st, (const uint64_t *)len.p, loff.p, nlines + 1)) != MCX_OK) return rc;
   uint64_t total = 0;
-  HIP_TRY(hipMemcpy(&total, loff.p + nlines, 8, hipMemcpyDeviceToHost));
+  if ((rc = scan_total(st, (const uint64_t *)len.p, loff.p, nlines + 1, &total)) != MCX_OK) return rc;
   len.release();
   DevBuf<uint8_t> text;  // sized by the scan
   HIP_TRY(text.alloc(std::max<uint64_t>(total, 1)));
   GRID_LAUNCH(k_cv_emit, nlines * 64, x, (const uint64_t *)loff.p, (uint64_t)0, nlines, text.p);
   if (line_off) HIP_TRY(hipMemcpyAsync(line_off, loff.p, 8 * (nlines + 1), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));  // the text is complete, the staging buffers are ours
-  HIP_TRY(hipStreamSynchronize(g->cstream));
-  const uint64_t chunk = std::min<uint64_t>(kStageBytes, g->stage_alloc) & ~15ull;
-  auto fetch = [&](uint64_t c0, int b) -> int {
-    HIP_TRY(hipMemcpyAsync(g->h_stage[b], text.p + c0, std::min(total, c0 + chunk) - c0, hipMemcpyDeviceToHost, g->cstream));
-    HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
-    return MCX_OK;
-  };
-  if ((rc = drain_to_sink(g, total, chunk, fetch, sink, ctx, "coverage sink failed")) != MCX_OK) return rc;  // (nothing is left in flight on the text either)
+  if ((rc = text_to_sink(g, text.p, total, sink, ctx, "coverage sink failed")) != MCX_OK) return rc;  // (nothing is left in flight on the text either)
   coverage_add_stats(stats_accum, nreads, B);
   return MCX_OK;
 }
@@ -4073,6 +4098,14 @@ extern "C" int mcx_graph_coverage_text(mcx_graph *g, const uint8_t *bases, const
 // ---------------------------------------------------------------------------
 // correct (ctx_correct.c): reads corrected against the graph -- mcx_correct.h
 // ---------------------------------------------------------------------------
+// the gap bounds that `correct` and `thread` (`what`) take
+static int gap_bounds_ok(const char *what, double gap_variance, double gap_wiggle)
+{
+  if (!std::isfinite(gap_variance) || !std::isfinite(gap_wiggle) || gap_variance < 0 || gap_wiggle < 0)
+    return fail(MCX_ERR_ARG, "%s: the gap variance and the gap wiggle must be finite and not negative", what);
+  return MCX_OK;
+}
+
 static int correct_begin(mcx_graph *g, const mcx_correct_params *p, mcx_correct_params *q)
 {
   int rc = lookup_begin(g, "correct");
@@ -4080,8 +4113,7 @@ static int correct_begin(mcx_graph *g, const mcx_correct_params *p, mcx_correct_
   if (!p) return fail(MCX_ERR_ARG, "correct: null parameters");
   if (p->colour >= (uint32_t)g->ncols) return fail(MCX_ERR_ARG, "correct: colour %u is not one of the graph's %d", p->colour, g->ncols);
   if (p->flags & ~(uint32_t)MCX_CORRECT_TWO_WAY) return fail(MCX_ERR_ARG, "correct: unknown flags 0x%x", p->flags);
-  if (!std::isfinite(p->gap_variance) || !std::isfinite(p->gap_wiggle) || p->gap_variance < 0 || p->gap_wiggle < 0)
-    return fail(MCX_ERR_ARG, "correct: the gap variance and the gap wiggle must be finite and not negative");
+  if ((rc = gap_bounds_ok("correct", p->gap_variance, p->gap_wiggle)) != MCX_OK) return rc;
   *q = *p;
   if (!q->fq_zero) q->fq_zero = '.';
   return MCX_OK;
@@ -4132,10 +4164,8 @@ static int correct_walks(mcx_graph *g, const CrView &x, CrWork &w, bool ends = t
     GRID_LAUNCH(k_th_tasks_count, n * 64, x, g->t, ntask.p, ncap.p, (const uint64_t *)nullptr, (const uint64_t *)nullptr, (CrTask *)nullptr,
                 (unsigned long long *)nullptr);
   int rc;
-  if ((rc = device_scan(st, (const uint64_t *)ntask.p, w.toff.p, n + 1)) != MCX_OK) return rc;
-  if ((rc = device_scan(st, (const uint64_t *)ncap.p, w.coff.p, n + 1)) != MCX_OK) return rc;
-  HIP_TRY(hipMemcpy(&w.ntasks, w.toff.p + n, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&w.ncap, w.coff.p + n, 8, hipMemcpyDeviceToHost));
+  if ((rc = scan_total(st, (const uint64_t *)ntask.p, w.toff.p, n + 1, &w.ntasks)) != MCX_OK) return rc;
+  if ((rc = scan_total(st, (const uint64_t *)ncap.p, w.coff.p, n + 1, &w.ncap)) != MCX_OK) return rc;
   ntask.release();
   ncap.release();
   HIP_TRY(w.tasks.alloc(std::max<uint64_t>(w.ntasks, 1)));
@@ -4207,9 +4237,44 @@ extern "C" int mcx_graph_correct_stream_dev(mcx_graph *g, const void *d_stream, 
 
 extern "C" uint64_t mcx_graph_correct_walk_steps(const mcx_graph *g) { return g ? g->cr_walk_steps : 0; }
 
-// Host reads through the pinned staging buffers as ASCII in the stand-alone chunks of mcx_chunk.h, as coverage_batch
-// takes them: a chunk is probed into scratch references indexed by its stream position and placed from there into the
-// batch's, so a read cut into pieces is whole before its tasks are made.  Synchronous.
+// what a batch of host reads leaves on the device for a CrView: the reads' offsets and, indexed by base position (off[0]
+// is position 0), their bases, their qualities if there are any, and the node references
+struct CrBatch {
+  DevBuf<uint64_t> boff, node;
+  DevBuf<uint8_t> seq, qual;
+};
+
+// Host reads in alone_chunks for `correct` and `thread` (`what`), as coverage_batch takes them: a chunk is probed into
+// scratch references indexed by its stream position and placed from there into the batch's, so a read cut into pieces
+// is whole before its tasks are made.  Nothing is synchronised: when this fails, the caller waits for the stream before
+// the batch goes.
+static int correct_batch(mcx_graph *g, const char *what, const uint8_t *bases, const uint8_t *quals, const uint64_t *off, uint64_t nreads,
+                         uint32_t colour, CrBatch &B)
+{
+  ChunkLayout lay;
+  int rc = place_layout(g, what, &lay);
+  if (rc != MCX_OK) return rc;
+  hipStream_t st = g->stream;
+  const uint64_t nbases = off[nreads] - off[0], pitch = std::max<uint64_t>(64, (nbases + 63) / 64 * 64), spitch = lay.cap;
+  DevBuf<uint64_t> snode;
+  HIP_TRY(B.node.alloc(pitch));
+  HIP_TRY(snode.alloc(spitch));
+  HIP_TRY(B.boff.alloc(nreads + 1));
+  HIP_TRY(B.seq.alloc(pitch));
+  if (quals) HIP_TRY(B.qual.alloc(pitch));
+  HIP_TRY(hipMemsetAsync(B.node.p, 0xff, 8 * pitch, st));
+  HIP_TRY(hipMemcpyAsync(B.boff.p, off, 8 * (nreads + 1), hipMemcpyHostToDevice, st));
+  if (nbases) HIP_TRY(hipMemcpyAsync(B.seq.p, bases + off[0], nbases, hipMemcpyHostToDevice, st));
+  if (nbases && quals) HIP_TRY(hipMemcpyAsync(B.qual.p, quals + off[0], nbases, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
+  return alone_chunks(g, lay, bases, off, nreads, [&](int, const Chunk &c, const uint8_t *d_stream, const uint64_t *d_off) -> int {
+    int rc2 = correct_probe(g, d_stream, c.L, colour, snode.p, spitch);
+    if (rc2 != MCX_OK) return rc2;
+    GRID_LAUNCH(k_cr_place, c.L, d_off, c.n, (const uint64_t *)B.boff.p, c.r0, c.shift, c.own, (const uint64_t *)snode.p, spitch, B.node.p, pitch);
+    return MCX_OK;
+  });  // (snode goes here: hipFree waits for the work that reads it)
+}
+
 extern "C" int mcx_graph_correct(mcx_graph *g, const uint8_t *bases, const uint8_t *quals, const uint64_t *off, uint64_t nreads,
                                  const mcx_correct_params *p, mcx_sink_fn sink, void *ctx, uint64_t *out_off, mcx_correct_stats *stats_accum)
 {
@@ -4219,77 +4284,35 @@ extern "C" int mcx_graph_correct(mcx_graph *g, const uint8_t *bases, const uint8
   if (!nreads) { if (out_off) out_off[0] = 0; return MCX_OK; }
   if (!off || !sink) return fail(MCX_ERR_ARG, "null read buffers");
   if (!bases && off[nreads] != off[0]) return fail(MCX_ERR_ARG, "null read buffers");
-  if ((rc = ensure_stage(g)) != MCX_OK) return rc;
   hipStream_t st = g->stream;
-  const uint64_t nbases = off[nreads] - off[0], pitch = std::max<uint64_t>(64, (nbases + 63) / 64 * 64);
-  // layout of a staging buffer: [0, C) stream | offsets (R + 1); R = C / 16 reads at most
-  ChunkLayout lay;
-  if ((rc = alone_layout(g, "correct", 1024, 64, 2, 3, &lay)) != MCX_OK) return rc;
-  const uint64_t C = lay.cap, R = lay.max_reads, off_at = C, spitch = C;
-  if (off_at + 8 * (R + 1) > g->stage_alloc) return fail(MCX_ERR_HIP, "correct: internal error in the staging layout");
-  DevBuf<uint64_t> node, snode, boff, len, ooff;
-  DevBuf<uint8_t> seq, qual, text;
+  CrBatch B;
+  DevBuf<uint64_t> len, ooff;
+  DevBuf<uint8_t> text;
   CrWork w;
   unsigned long long cnt[2] = {0, 0}, ctr[kCrAllCounters];
   uint64_t total = 0;
   auto run = [&]() -> int {
-    HIP_TRY(node.alloc(pitch));
-    HIP_TRY(snode.alloc(spitch));
-    HIP_TRY(boff.alloc(nreads + 1));
-    HIP_TRY(seq.alloc(pitch));
-    if (quals) HIP_TRY(qual.alloc(pitch));
-    HIP_TRY(hipMemsetAsync(node.p, 0xff, 8 * pitch, st));
-    HIP_TRY(hipMemcpyAsync(boff.p, off, 8 * (nreads + 1), hipMemcpyHostToDevice, st));
-    if (nbases) HIP_TRY(hipMemcpyAsync(seq.p, bases + off[0], nbases, hipMemcpyHostToDevice, st));
-    if (nbases && quals) HIP_TRY(hipMemcpyAsync(qual.p, quals + off[0], nbases, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
-    ReadChunker ck(bases, off, nreads);
-    while (!ck.done()) {
-      int b;
-      int rc2 = next_stage(g, &b);
-      if (rc2 != MCX_OK) return rc2;
-      uint8_t *hs = g->h_stage[b];
-      uint64_t *ho = reinterpret_cast<uint64_t *>(hs + off_at);
-      const Chunk c = ck.fill(lay, hs, ho);
-      const uint64_t own = c.piece_of >= 0 && !c.ended ? c.take - lay.overlap : ~0ull;  // (whole reads and last pieces own all of their own)
-      uint8_t *ds = g->d_stage[b];
-      HIP_TRY(hipMemcpyAsync(ds, hs, c.L, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(ds + off_at, ho, 8 * (c.n + 1), hipMemcpyHostToDevice, st));
-      if ((rc2 = correct_probe(g, ds, c.L, q.colour, snode.p, spitch)) != MCX_OK) return rc2;
-      GRID_LAUNCH(k_cr_place, c.L, reinterpret_cast<const uint64_t *>(ds + off_at), c.n, (const uint64_t *)boff.p, c.r0, c.shift, own,
-                  (const uint64_t *)snode.p, spitch, node.p, pitch);
-      HIP_TRY(hipEventRecord(g->ev[b], st));
-    }
-    snode.release();  // (hipFree waits for the work that reads it)
-    const CrView x{boff.p, nreads, 0, g->k, node.p, seq.p, quals ? qual.p : nullptr, (uint32_t)g->ncols, q.colour, q.flags,
-                   q.gap_variance, q.gap_wiggle, (uint8_t)q.fq_zero};
-    int rc2 = correct_walks(g, x, w);
+    int rc2 = correct_batch(g, "correct", bases, quals, off, nreads, q.colour, B);
     if (rc2 != MCX_OK) return rc2;
+    const CrView x{B.boff.p, nreads, 0, g->k, B.node.p, B.seq.p, B.qual.p, (uint32_t)g->ncols, q.colour, q.flags,
+                   q.gap_variance, q.gap_wiggle, (uint8_t)q.fq_zero};
+    if ((rc2 = correct_walks(g, x, w)) != MCX_OK) return rc2;
     HIP_TRY(len.alloc(nreads + 1));
     HIP_TRY(ooff.alloc(nreads + 1));
     HIP_TRY(hipMemsetAsync(len.p + nreads, 0, 8, st));
     GRID_LAUNCH(k_cr_len, nreads * 64, x, (const CrTask *)w.tasks.p, (const CrRes *)w.res.p, (const uint64_t *)w.toff.p, len.p, w.ctr.p);
-    if ((rc2 = device_scan(st, (const uint64_t *)len.p, ooff.p, nreads + 1)) != MCX_OK) return rc2;
-    HIP_TRY(hipMemcpy(&total, ooff.p + nreads, 8, hipMemcpyDeviceToHost));
+    if ((rc2 = scan_total(st, (const uint64_t *)len.p, ooff.p, nreads + 1, &total)) != MCX_OK) return rc2;
     HIP_TRY(text.alloc(std::max<uint64_t>(total, 1)));  // sized by the scan
     GRID_LAUNCH(k_cr_emit, nreads * 64, x, (const CrTask *)w.tasks.p, (const CrRes *)w.res.p, (const uint8_t *)w.codes.p, (const uint64_t *)w.toff.p,
                 (const uint64_t *)ooff.p, text.p);
     if (out_off) HIP_TRY(hipMemcpyAsync(out_off, ooff.p, 8 * (nreads + 1), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(cnt, g->d_rt_cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));  // the records are complete, the staging buffers are ours
-    HIP_TRY(hipStreamSynchronize(g->cstream));
     return MCX_OK;
   };
   rc = run();
   if (rc != MCX_OK) { (void)hipStreamSynchronize(st); return rc; }  // before the scratch goes
-  const uint64_t chunk = std::min<uint64_t>(kStageBytes, g->stage_alloc) & ~15ull;
-  auto fetch = [&](uint64_t c0, int b) -> int {
-    HIP_TRY(hipMemcpyAsync(g->h_stage[b], text.p + c0, std::min(total, c0 + chunk) - c0, hipMemcpyDeviceToHost, g->cstream));
-    HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
-    return MCX_OK;
-  };
-  if ((rc = drain_to_sink(g, total, chunk, fetch, sink, ctx, "correct sink failed")) != MCX_OK) return rc;
+  if ((rc = text_to_sink(g, text.p, total, sink, ctx, "correct sink failed")) != MCX_OK) return rc;
   correct_add_stats(g, stats_accum, nreads, cnt, ctr);
   return MCX_OK;
 }
@@ -4355,9 +4378,8 @@ static int th_sort_reduce(mcx_graph *g, const ThLink *in, uint64_t m, uint64_t n
   HIP_TRY(head.alloc(nvalid + 1));
   HIP_TRY(ex.alloc(nvalid + 1));
   GRID_LAUNCH(k_th_heads, nvalid + 1, in, (const uint64_t *)perm, nvalid, head.p);
-  if ((rc = device_scan(st, (const uint8_t *)head.p, ex.p, nvalid + 1)) != MCX_OK) return rc;
   uint64_t nruns = 0, words = 0;
-  HIP_TRY(hipMemcpy(&nruns, ex.p + nvalid, 8, hipMemcpyDeviceToHost));
+  if ((rc = scan_total(st, (const uint8_t *)head.p, ex.p, nvalid + 1, &nruns)) != MCX_OK) return rc;
   k0.release();
   k1.release();
   tmp.release();
@@ -4369,8 +4391,7 @@ static int th_sort_reduce(mcx_graph *g, const ThLink *in, uint64_t m, uint64_t n
   HIP_TRY(hipMalloc((void **)&s.links, nruns * sizeof(ThLink)));
   GRID_LAUNCH(k_th_runs, nvalid + 1, (const uint8_t *)head.p, (const uint64_t *)ex.p, nvalid, runstart.p);
   GRID_LAUNCH(k_th_reduce, nruns + 1, in, (const uint64_t *)perm, (const uint64_t *)runstart.p, nruns, s.links, nwords.p);
-  if ((rc = device_scan(st, (const uint64_t *)nwords.p, woff.p, nruns + 1)) != MCX_OK) return rc;
-  HIP_TRY(hipMemcpy(&words, woff.p + nruns, 8, hipMemcpyDeviceToHost));
+  if ((rc = scan_total(st, (const uint64_t *)nwords.p, woff.p, nruns + 1, &words)) != MCX_OK) return rc;
   HIP_TRY(hipMalloc((void **)&s.pool, (words + 1) * 8));
   HIP_TRY(hipMemsetAsync(s.pool, 0, (words + 1) * 8, st));
   GRID_LAUNCH(k_th_copy, nruns, s.links, (const uint64_t *)woff.p, nruns, s.pool);
@@ -4422,8 +4443,7 @@ static int thread_begin(mcx_graph *g, const mcx_thread_params *p, uint32_t *max_
   if (!p) return fail(MCX_ERR_ARG, "thread: null parameters");
   if (g->ncols != 1) return fail(MCX_ERR_ARG, "thread: links are made over a graph of one colour, this one has %d", g->ncols);
   if (p->flags & ~(uint32_t)MCX_THREAD_TWO_WAY) return fail(MCX_ERR_ARG, "thread: unknown flags 0x%x", p->flags);
-  if (!std::isfinite(p->gap_variance) || !std::isfinite(p->gap_wiggle) || p->gap_variance < 0 || p->gap_wiggle < 0)
-    return fail(MCX_ERR_ARG, "thread: the gap variance and the gap wiggle must be finite and not negative");
+  if ((rc = gap_bounds_ok("thread", p->gap_variance, p->gap_wiggle)) != MCX_OK) return rc;
   if (p->max_juncs > kThMaxJuncs) return fail(MCX_ERR_ARG, "thread: a link holds %u junctions at the most (max_juncs = %u)", kThMaxJuncs, p->max_juncs);
   *max_juncs = p->max_juncs ? p->max_juncs : kThMaxJuncs;
   if (!g->links) {
@@ -4452,9 +4472,8 @@ static int thread_links(mcx_graph *g, const CrView &x, const CrWork &w, uint32_t
   GRID_LAUNCH(k_th_nodes<false>, nreads * 64, x, g->t, (const CrTask *)w.tasks.p, (const CrRes *)w.res.p, (const uint64_t *)w.refs.p,
               (const uint64_t *)w.toff.p, (const uint64_t *)nullptr, nnode.p, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr,
               (unsigned long long *)nullptr, d_tc.p);
-  if ((rc = device_scan(st, (const uint64_t *)nnode.p, noff.p, nreads + 1)) != MCX_OK) return rc;
   uint64_t nn = 0;
-  HIP_TRY(hipMemcpy(&nn, noff.p + nreads, 8, hipMemcpyDeviceToHost));
+  if ((rc = scan_total(st, (const uint64_t *)nnode.p, noff.p, nreads + 1, &nn)) != MCX_OK) return rc;
   HIP_TRY(hipMemcpy(tc, d_tc.p, kThAllCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   if (!nn) return MCX_OK;
   if (tc[kThMaxNodes] + 1 > S->hist_cap) {  // the histogram grows to the longest contig there can be
@@ -4485,11 +4504,9 @@ static int thread_links(mcx_graph *g, const CrView &x, const CrWork &w, uint32_t
   HIP_TRY(hipMemsetAsync(fwf.p + nn, 0, 1, st));
   HIP_TRY(hipMemsetAsync(rvf.p + nn, 0, 1, st));
   GRID_LAUNCH_W(k_th_junc, nn, g->t, g->k, (const uint64_t *)cn.p, (const uint64_t *)cs.p, (const uint64_t *)cend.p, nn, fwf.p, rvf.p, fwb.p, rvb.p, d_tc.p);
-  if ((rc = device_scan(st, (const uint8_t *)fwf.p, fwx.p, nn + 1)) != MCX_OK) return rc;
-  if ((rc = device_scan(st, (const uint8_t *)rvf.p, rvx.p, nn + 1)) != MCX_OK) return rc;
   uint64_t nfw = 0, nrv = 0;
-  HIP_TRY(hipMemcpy(&nfw, fwx.p + nn, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&nrv, rvx.p + nn, 8, hipMemcpyDeviceToHost));
+  if ((rc = scan_total(st, (const uint8_t *)fwf.p, fwx.p, nn + 1, &nfw)) != MCX_OK) return rc;
+  if ((rc = scan_total(st, (const uint8_t *)rvf.p, rvx.p, nn + 1, &nrv)) != MCX_OK) return rc;
   if (nfw && nrv) {
     const uint64_t wf = nfw / 32 + 2, wr = nrv / 32 + 2;
     HIP_TRY(pf.alloc(wf));
@@ -4512,7 +4529,7 @@ static int thread_links(mcx_graph *g, const CrView &x, const CrWork &w, uint32_t
   return th_merge(g, false);
 }
 
-// Host reads in the chunks of mcx_graph_correct; passes A-C are its own, without the end extensions.  Synchronous.
+// Host reads in a correct_batch; passes A-C are `correct`'s, without the end extensions.  Synchronous.
 extern "C" int mcx_graph_thread(mcx_graph *g, const uint8_t *bases, const uint64_t *off, uint64_t nreads, const mcx_thread_params *p,
                                 mcx_thread_stats *stats_accum)
 {
@@ -4522,48 +4539,16 @@ extern "C" int mcx_graph_thread(mcx_graph *g, const uint8_t *bases, const uint64
   if (!nreads) return MCX_OK;
   if (!off) return fail(MCX_ERR_ARG, "null read buffers");
   if (!bases && off[nreads] != off[0]) return fail(MCX_ERR_ARG, "null read buffers");
-  if ((rc = ensure_stage(g)) != MCX_OK) return rc;
   hipStream_t st = g->stream;
-  const uint64_t nbases = off[nreads] - off[0], pitch = std::max<uint64_t>(64, (nbases + 63) / 64 * 64);
-  ChunkLayout lay;
-  if ((rc = alone_layout(g, "thread", 1024, 64, 2, 3, &lay)) != MCX_OK) return rc;
-  const uint64_t C = lay.cap, R = lay.max_reads, off_at = C, spitch = C;
-  if (off_at + 8 * (R + 1) > g->stage_alloc) return fail(MCX_ERR_HIP, "thread: internal error in the staging layout");
-  DevBuf<uint64_t> node, snode, boff;
-  DevBuf<uint8_t> seq;
+  CrBatch B;
   CrWork w;
   unsigned long long cnt[2] = {0, 0}, ctr[kCrAllCounters], tc[kThAllCounters] = {0};
   auto run = [&]() -> int {
-    HIP_TRY(node.alloc(pitch));
-    HIP_TRY(snode.alloc(spitch));
-    HIP_TRY(boff.alloc(nreads + 1));
-    HIP_TRY(seq.alloc(pitch));
-    HIP_TRY(hipMemsetAsync(node.p, 0xff, 8 * pitch, st));
-    HIP_TRY(hipMemcpyAsync(boff.p, off, 8 * (nreads + 1), hipMemcpyHostToDevice, st));
-    if (nbases) HIP_TRY(hipMemcpyAsync(seq.p, bases + off[0], nbases, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(g->d_rt_cnt, 0, 2 * sizeof(unsigned long long), st));
-    ReadChunker ck(bases, off, nreads);
-    while (!ck.done()) {
-      int b;
-      int rc2 = next_stage(g, &b);
-      if (rc2 != MCX_OK) return rc2;
-      uint8_t *hs = g->h_stage[b];
-      uint64_t *ho = reinterpret_cast<uint64_t *>(hs + off_at);
-      const Chunk c = ck.fill(lay, hs, ho);
-      const uint64_t own = c.piece_of >= 0 && !c.ended ? c.take - lay.overlap : ~0ull;  // (whole reads and last pieces own all of their own)
-      uint8_t *ds = g->d_stage[b];
-      HIP_TRY(hipMemcpyAsync(ds, hs, c.L, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(ds + off_at, ho, 8 * (c.n + 1), hipMemcpyHostToDevice, st));
-      if ((rc2 = correct_probe(g, ds, c.L, 0, snode.p, spitch)) != MCX_OK) return rc2;
-      GRID_LAUNCH(k_cr_place, c.L, reinterpret_cast<const uint64_t *>(ds + off_at), c.n, (const uint64_t *)boff.p, c.r0, c.shift, own,
-                  (const uint64_t *)snode.p, spitch, node.p, pitch);
-      HIP_TRY(hipEventRecord(g->ev[b], st));
-    }
-    snode.release();  // (hipFree waits for the work that reads it)
-    const CrView x{boff.p, nreads, 0, g->k, node.p, seq.p, nullptr, 1u, 0u, (p->flags & MCX_THREAD_TWO_WAY) ? kCrTwoWay : 0u,
-                   p->gap_variance, p->gap_wiggle, (uint8_t)'.'};
-    int rc2 = correct_walks(g, x, w, false);
+    int rc2 = correct_batch(g, "thread", bases, nullptr, off, nreads, 0, B);
     if (rc2 != MCX_OK) return rc2;
+    const CrView x{B.boff.p, nreads, 0, g->k, B.node.p, B.seq.p, nullptr, 1u, 0u, (p->flags & MCX_THREAD_TWO_WAY) ? kCrTwoWay : 0u,
+                   p->gap_variance, p->gap_wiggle, (uint8_t)'.'};
+    if ((rc2 = correct_walks(g, x, w, false)) != MCX_OK) return rc2;
     HIP_TRY(hipMemcpyAsync(cnt, g->d_rt_cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, st));
     if ((rc2 = thread_links(g, x, w, max_juncs, tc)) != MCX_OK) return rc2;
@@ -4671,20 +4656,11 @@ extern "C" int mcx_graph_links_text(mcx_graph *g, uint32_t flags, mcx_sink_fn si
   HIP_TRY(loff.alloc(s->n + 1));
   HIP_TRY(hipMemsetAsync(len.p + s->n, 0, 8, st));
   if ((rc = th_text_launch<false>(g, s, flags, len.p, nullptr, nullptr)) != MCX_OK) return rc;
-  if ((rc = device_scan(st, (const uint64_t *)len.p, loff.p, s->n + 1)) != MCX_OK) return rc;
-  HIP_TRY(hipMemcpy(&total, loff.p + s->n, 8, hipMemcpyDeviceToHost));
+  if ((rc = scan_total(st, (const uint64_t *)len.p, loff.p, s->n + 1, &total)) != MCX_OK) return rc;
   len.release();
   HIP_TRY(text.alloc(std::max<uint64_t>(total, 1)));  // sized by the scan
   if ((rc = th_text_launch<true>(g, s, flags, nullptr, loff.p, text.p)) != MCX_OK) { (void)hipStreamSynchronize(st); return rc; }
-  HIP_TRY(hipStreamSynchronize(st));  // the text is complete, the staging buffers are ours
-  HIP_TRY(hipStreamSynchronize(g->cstream));
-  const uint64_t chunk = std::min<uint64_t>(kStageBytes, g->stage_alloc) & ~15ull;
-  auto fetch = [&](uint64_t c0, int b) -> int {
-    HIP_TRY(hipMemcpyAsync(g->h_stage[b], text.p + c0, std::min(total, c0 + chunk) - c0, hipMemcpyDeviceToHost, g->cstream));
-    HIP_TRY(hipEventRecord(g->ev_copy[b], g->cstream));
-    return MCX_OK;
-  };
-  return drain_to_sink(g, total, chunk, fetch, sink, ctx, "links sink failed");
+  return text_to_sink(g, text.p, total, sink, ctx, "links sink failed");
 }
 
 extern "C" int mcx_graph_links_reset(mcx_graph *g)

@@ -6,10 +6,11 @@
 //    the first), then whole reads each followed by a separator.  A read that does not fit a chunk is cut into contiguous
 //    pieces, each a chunk of its own, with no separator until the read ends.  kChunkPad separators follow the chunk, so
 //    the 16-byte loads of the kernels stay inside the copy.  The buffer holds kCarry + cap + kChunkPad bytes.
-//  * stand-alone (mcx_graph_reads_touch, coverage_batch): no carry, every chunk is a stream of its own.  Whole reads each
-//    followed by a separator, or ONE piece of a read that does not fit, also followed by a separator; consecutive pieces
-//    overlap by k - 1 bases, so every k-mer of the read starts in exactly one piece: a piece owns all its positions but
-//    the last k - 1, the last piece of a read all of its own.  The buffer holds cap bytes.
+//  * stand-alone (alone_chunks of mcx_api.hip: mcx_graph_reads_touch, coverage_batch, and correct_batch for `correct` and
+//    `thread`): no carry, every chunk is a stream of its own.  Whole reads each followed by a separator, or ONE piece of a
+//    read that does not fit, also followed by a separator; consecutive pieces overlap by k - 1 bases, so every k-mer of
+//    the read starts in exactly one piece: a piece owns all its positions but the last k - 1, the last piece of a read
+//    all of its own (Chunk::own).  The buffer holds cap bytes.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -35,6 +36,9 @@ struct Chunk {
   long long piece_of = -1;  // >= 0: the chunk is a piece, `take` bases of this read from base `shift` on; ended = they are its last
   uint64_t shift = 0, take = 0;
   bool ended = false;
+  // The first `own` positions of each read in the chunk are the chunk's own: all of them (~0) for whole reads and for the
+  // piece that ends its read; a piece before that leaves its last `overlap` positions to the next piece, which starts there.
+  uint64_t own = ~0ull;
 };
 
 struct ReadChunker {
@@ -74,12 +78,13 @@ struct ReadChunker {
       c.shift = r_pos;
       c.take = std::min(len - r_pos, lay.cap - 1);
       c.ended = r_pos + c.take == len;
+      if (!c.ended) c.own = c.take - lay.overlap;
       memcpy(hs, bases + off[r] + r_pos, c.take);
       c.L = c.take;
       if (c.ended || lay.piece_sep) hs[c.L++] = '\n';
       c.n = lay.piece_sep ? 1 : 0;
       if (c.ended) { r++; r_pos = 0; }
-      else r_pos += c.take - lay.overlap;
+      else r_pos += c.own;
       break;
     }
     if (offs) offs[c.n] = lay.prefix + c.L;

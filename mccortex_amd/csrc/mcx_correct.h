@@ -18,7 +18,7 @@
 //   A. k_cr_probe   rt_probe's walk (mcx_reads.h) with a sink that keeps the slots: per stream position one 64-bit node
 //                   reference, slot << 1 | orient, all ones where there is no key or the key is not in the sample
 //      k_cr_place   (host entry) a chunk's references, indexed by stream position, into the batch's, indexed by base
-//                   position, as k_cv_place does
+//                   position (rt_place of mcx_reads.h, as k_cv_place)
 //   B. k_cr_tasks   a wave per read: its segments (db_alignment_next_gap) and its walk tasks, first counted, then, behind
 //                   two scans, written: the left extension, every gap with its bounds, the right extension.  A task owns
 //                   a range of gap_max + 2 (or the extension's limit) path entries.
@@ -75,25 +75,11 @@ __global__ __launch_bounds__(kThreads) void k_cr_probe(StreamArgs a, TableView t
   rt_probe<W>(a, t, CrRefSink{t, colour, pitch, node}, cnt);
 }
 
-// k_cv_place for the node references: read i of a chunk sits at the chunk's stream positions [so[i], so[i + 1] - 1) and
-// is read r0 + i of the batch; its first `own` positions go to base position boff[r0 + i] - boff[0] + shift.
+// rt_place (mcx_reads.h) for the node references
 __global__ __launch_bounds__(256) void k_cr_place(const uint64_t *so, uint64_t n, const uint64_t *boff, uint64_t r0, uint64_t shift, uint64_t own,
                                                   const uint64_t *snode, uint64_t spitch, uint64_t *node, uint64_t pitch)
 {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, np = so[n];
-  const uint64_t b0 = boff[0];
-  for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < np; p += stride) {
-    uint64_t lo = 0, hi = n;  // the last i with so[i] <= p
-    while (hi - lo > 1) {
-      const uint64_t mid = (lo + hi) >> 1;
-      if (so[mid] <= p) lo = mid; else hi = mid;
-    }
-    const uint64_t q = p - so[lo], len = so[lo + 1] - so[lo] - 1;
-    if (q >= (own < len ? own : len)) continue;  // the separator, or the tail that the next piece owns
-    const uint64_t d = boff[r0 + lo] - b0 + shift + q;
-    if (d >= pitch || p >= spitch) continue;
-    node[d] = snode[p];
-  }
+  rt_place(so, n, boff, r0, shift, own, spitch, pitch, [&](uint64_t p, uint64_t d) { node[d] = snode[p]; });
 }
 
 // A batch on the device.  Read r holds the positions [boff[r] - boff[0], boff[r + 1] - boff[0] - sep) of node, seq and

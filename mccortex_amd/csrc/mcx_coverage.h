@@ -7,8 +7,8 @@
 //                   words of its 16 start positions and stores 64 bytes of coverage and 16 bytes of edges, so a wave
 //                   writes 4 KB and 1 KB contiguous per colour.  Every position of every tile walked is written.
 //      k_cv_place   (host entries only) a chunk's arrays, indexed by the chunk's stream position, into the batch's,
-//                   indexed by base position: the separators drop out, a piece of a long read lands behind the one
-//                   before it.
+//                   indexed by base position (rt_place of mcx_reads.h): the separators drop out, a piece of a long read
+//                   lands behind the one before it.
 //   B. k_cv_len     the length of every line; a 64-bit exclusive scan of them gives line_off
 //      k_cv_emit    a wave per line writes its text at line_off
 // All are grid-stride loops (the "grid" knob caps the launches); the table is only read.
@@ -58,31 +58,17 @@ __global__ __launch_bounds__(kThreads) void k_cv_probe(StreamArgs a, TableView t
   rt_probe<W>(a, t, CvGatherSink{t, ncols, pitch, covg, edges}, cnt);
 }
 
-// A chunk of n reads (or one piece of a read): read i of it sits at the chunk's stream positions [so[i], so[i + 1] - 1)
-// and is read r0 + i of the batch.  Of every read the first `own` positions (all of them when own = ~0) go to the
-// batch's arrays at base position boff[r0 + i] - boff[0] + shift.  One thread per stream position finds its read by
-// bisection (the lanes of a wave mostly meet the same few offsets).
+// rt_place (mcx_reads.h) for the coverage and the edges of every colour
 __global__ __launch_bounds__(256) void k_cv_place(const uint64_t *so, uint64_t n, const uint64_t *boff, uint64_t r0, uint64_t shift, uint64_t own,
                                                   uint32_t ncols, const uint32_t *scovg, const uint8_t *sedges, uint64_t spitch, uint32_t *covg,
                                                   uint8_t *edges, uint64_t pitch)
 {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, np = so[n];
-  const uint64_t b0 = boff[0];
-  for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < np; p += stride) {
-    uint64_t lo = 0, hi = n;  // the last i with so[i] <= p
-    while (hi - lo > 1) {
-      const uint64_t mid = (lo + hi) >> 1;
-      if (so[mid] <= p) lo = mid; else hi = mid;
-    }
-    const uint64_t q = p - so[lo], len = so[lo + 1] - so[lo] - 1;
-    if (q >= (own < len ? own : len)) continue;  // the separator, or the tail that the next piece owns
-    const uint64_t d = boff[r0 + lo] - b0 + shift + q;
-    if (d >= pitch || p >= spitch) continue;
+  rt_place(so, n, boff, r0, shift, own, spitch, pitch, [&](uint64_t p, uint64_t d) {
     for (uint32_t c = 0; c < ncols; c++) {
       covg[(uint64_t)c * pitch + d] = scovg[(uint64_t)c * spitch + p];
       if (edges) edges[(uint64_t)c * pitch + d] = sedges[(uint64_t)c * spitch + p];
     }
-  }
+  });
 }
 
 // ---- the text ------------------------------------------------------------------------------------------------------

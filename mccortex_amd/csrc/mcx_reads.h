@@ -143,6 +143,33 @@ template <int W> __global__ __launch_bounds__(kThreads) void k_rt_probe(StreamAr
   rt_probe<W>(a, t, RtMaskSink{hit}, cnt);
 }
 
+// What a sink of rt_probe left per stream position of a chunk, placed by base position (k_cv_place, k_cr_place; host
+// entries only).  The chunk holds n reads (or one piece of a read): read i of it sits at the chunk's stream positions
+// [so[i], so[i + 1] - 1) and is read r0 + i of the batch.  Of every read the first `own` positions (all of them when
+// own = ~0, Chunk::own of mcx_chunk.h) go to the batch's arrays at base position boff[r0 + i] - boff[0] + shift: the
+// separators drop out, a piece of a long read lands behind the one before it.  copy(p, d) moves stream position p
+// (< spitch) to base position d (< pitch).  One thread per stream position finds its read by bisection (the lanes of a
+// wave mostly meet the same few offsets).
+template <class Copy>
+__device__ __forceinline__ void rt_place(const uint64_t *so, uint64_t n, const uint64_t *boff, uint64_t r0, uint64_t shift, uint64_t own,
+                                         uint64_t spitch, uint64_t pitch, const Copy &copy)
+{
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, np = so[n];
+  const uint64_t b0 = boff[0];
+  for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < np; p += stride) {
+    uint64_t lo = 0, hi = n;  // the last i with so[i] <= p
+    while (hi - lo > 1) {
+      const uint64_t mid = (lo + hi) >> 1;
+      if (so[mid] <= p) lo = mid; else hi = mid;
+    }
+    const uint64_t q = p - so[lo], len = so[lo + 1] - so[lo] - 1;
+    if (q >= (own < len ? own : len)) continue;  // the separator, or the tail that the next piece owns
+    const uint64_t d = boff[r0 + lo] - b0 + shift + q;
+    if (d >= pitch || p >= spitch) continue;
+    copy(p, d);
+  }
+}
+
 // bits [s, e) of the bit array `m` that fall into its 64-bit word w (s < e, w in [s / 64, (e - 1) / 64])
 __device__ __forceinline__ uint64_t rt_word(const uint64_t *m, uint64_t w, uint64_t s, uint64_t e)
 {

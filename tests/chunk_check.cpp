@@ -139,6 +139,7 @@ static void check_alone(uint64_t k, uint64_t C)
   ReadChunker ck(in.data(), in.off.data(), nreads);
   Seen seen;
   uint64_t next = 0, owned = 0;  // next read, start positions of it that earlier pieces own
+  std::vector<int> cover;        // of the read in pieces: how many pieces own each base position
   while (!ck.done()) {
     const Chunk c = ck.fill(lay, buf.get(), ho.get());
     seen.chunks++;
@@ -156,10 +157,25 @@ static void check_alone(uint64_t k, uint64_t C)
       // own: all positions but the last k - 1; the last piece owns all of its own.  [shift, shift + own) tile [0, len).
       CHECK(c.ended || c.take > k1, "a piece owns nothing");
       const uint64_t own = c.ended ? c.take : c.take - k1;
-      if (c.ended) { CHECK(owned + own == len, "tiling"); seen.full_last_piece += c.take == C - 1; next++; owned = 0; }
-      else { seen.mid_piece++; owned += own; }
+      // what the chunk says it owns, [shift, shift + min(own, take)), is that range: every base position of the read
+      // falls into exactly one piece's, and the ranges come in order
+      if (c.shift == 0) cover.assign(len, 0);
+      CHECK(c.own == (c.ended ? ~0ull : own), "Chunk::own = %llu", (unsigned long long)c.own);
+      CHECK(c.shift == owned && c.shift + std::min(c.own, c.take) <= len, "owned range");
+      for (uint64_t p = c.shift; p < c.shift + std::min(c.own, c.take); p++) cover[p]++;
+      if (c.ended) {
+        CHECK(owned + own == len, "tiling");
+        for (uint64_t p = 0; p < len; p++) CHECK(cover[p] == 1, "position %llu of read %llu is owned %d times", (unsigned long long)p, (unsigned long long)next, cover[p]);
+        seen.full_last_piece += c.take == C - 1;
+        next++;
+        owned = 0;
+      } else {
+        seen.mid_piece++;
+        owned += own;
+      }
     } else {
       CHECK(owned == 0, "whole reads inside a read in pieces");
+      CHECK(c.own == ~0ull, "whole reads own all of their own");
       for (uint64_t i = 0; i < c.n; i++) {
         const uint64_t len = in.len(next + i);
         CHECK(ho[i + 1] == ho[i] + len + 1 && buf[ho[i + 1] - 1] == '\n', "read %llu: offsets", (unsigned long long)(next + i));
