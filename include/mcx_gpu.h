@@ -31,7 +31,8 @@ typedef enum {
   MCX_ERR_NOMEM = -3,     /* device/host allocation failed */
   MCX_ERR_FULL = -4,      /* "Hash table is full" (src/graph/hash_table.c:119-123) */
   MCX_ERR_HIP = -5,       /* HIP runtime error, see mcx_last_error() */
-  MCX_ERR_SINK = -6       /* export sink returned non-zero */
+  MCX_ERR_SINK = -6,      /* export sink returned non-zero */
+  MCX_ERR_INVAL = -7      /* malformed input text (mcx_links_add_text; see mcx_links_error) */
 } mcx_status;
 
 /* Subset of SeqLoadingStats (src/basic/seq_loading_stats.h:5-14) that the
@@ -727,6 +728,61 @@ int mcx_join_add_records(mcx_join *j, int source, const void *recs, uint64_t nre
                          const int32_t *from_col, const int32_t *into_col, int nmap);
 int mcx_join_finish(mcx_join *j, mcx_sink_fn sink, void *ctx, mcx_join_stats *stats);
 void mcx_join_destroy(mcx_join *j);
+
+/* `links` (src/commands/ctx_links.c, src/paths/link_tree.c): clean, list and count the links of a version-4 .ctp body,
+ * one colour.  No graph handle and no table: a k-mer is its ordinal within a piece, the per-k-mer trie of junction
+ * strings is a sorted list with longest-common-prefix values (mcx_links.h).
+ *   mcx_links_create      kmer_size: the k of the file (odd, any size: k-mers stay text).
+ *   mcx_links_configure   test knobs, the answers must not change with them: "grid" (at most n blocks per launch, 0 =
+ *       CUs x 8) and "out_chunk" (bytes of text per sink call, 0 = 64 MiB; a seam may fall inside a line).
+ *   mcx_links_buffer      pinned host memory of `bytes` bytes owned by the handle (one at a time; freed by the next call
+ *       and by destroy), which the reader fills.
+ *   mcx_links_add_text    `text`: whole k-mer blocks of the body (`<kmer> <n>` lines, each followed by its link lines
+ *       `<F|R> <njuncs> <count> <juncs> seq=<..> juncpos=<..>`); begins at a line start and ends behind a newline; `#`
+ *       comment lines and empty lines anywhere.  flags: MCX_LINKS_CLEAN (tree links with a count below `cutoff` go),
+ *       MCX_LINKS_HIST (every tree link with dist < distsize adds one to hist[dist][min(count, covgsize - 1)], before
+ *       cleaning).  max_kmers: the k-mers of this piece beyond that many are ignored with their lines (0 = no limit).
+ *       ctp_sink gets the .ctp lines of the written links in file order of the k-mers (a link is written iff no other
+ *       input link of its k-mer and orientation extends it and its summed count is at least the cut-off; the `<kmer>
+ *       <n>` line is left out with the block when n is 0), list_sink the rows `<k + dist + 1>,<count>` of the tree
+ *       links that survive; either may be NULL.  Statistics are gathered either way.  Synchronous.  MCX_ERR_INVAL for a
+ *       malformed line: nothing of the piece is counted or delivered.
+ *   mcx_links_get_stats   the totals so far.
+ *   mcx_links_hist        distsize x covgsize counters, accumulated over the calls (the sizes of the first
+ *       MCX_LINKS_HIST call hold for the handle).
+ *   mcx_links_error       after MCX_ERR_INVAL: the refusal (MCX_LINKS_BAD_*) and the byte offset, within the text of that
+ *       call, of the first bad line in file order.
+ *   mcx_links_phases      host-clock milliseconds so far of the eight phases (tools/bench_links.py): upload, lines,
+ *       parse, sort, reduce + lcp, tree links (histogram, list), what is written, .ctp text. */
+typedef struct mcx_links mcx_links;
+enum { MCX_LINKS_CLEAN = 1, MCX_LINKS_HIST = 2 };
+enum {
+  MCX_LINKS_BAD_KMER_LINE = 1,    /* k-mer line not ACGT{k} <int> */
+  MCX_LINKS_BAD_ORIENT = 2,       /* first column not a lone F or R */
+  MCX_LINKS_BAD_NUMBER = 3,       /* njuncs or count not a number */
+  MCX_LINKS_MULTI_COLOUR = 4,     /* a comma in the count column: "Can only clean a single colour" */
+  MCX_LINKS_BAD_JUNCTION = 5,     /* non-ACGT junctions */
+  MCX_LINKS_NJUNCS_RANGE = 6,     /* njuncs of 0 or above 32767 */
+  MCX_LINKS_NJUNCS_LENGTH = 7,    /* njuncs != length of the junction string */
+  MCX_LINKS_NO_SEQ = 8,           /* no seq= tag */
+  MCX_LINKS_NO_JUNCPOS = 9,       /* no juncpos= tag */
+  MCX_LINKS_JUNCPOS_COUNT = 10,   /* juncpos is no list of njuncs numbers */
+  MCX_LINKS_SEQ_LENGTH = 11,      /* strlen(seq) != k + juncpos[last] + 1 */
+  MCX_LINKS_SEQ_BASE = 12,        /* seq[k + juncpos[i]] != juncs[i] */
+  MCX_LINKS_LINK_BEFORE_KMER = 13 /* a link line before any k-mer line */
+};
+typedef struct { uint32_t flags, distsize, covgsize, reserved; uint64_t cutoff, max_kmers; } mcx_links_params;
+typedef struct { uint64_t kmers_read, kmers_with_links, links, link_bytes, tree_links, links_in; } mcx_links_stats;
+int mcx_links_create(mcx_links **l, int kmer_size, int device);
+int mcx_links_configure(mcx_links *l, const char *key, uint64_t value);
+int mcx_links_buffer(mcx_links *l, size_t bytes, void **ptr);
+int mcx_links_add_text(mcx_links *l, const void *text, uint64_t nbytes, const mcx_links_params *p, mcx_sink_fn ctp_sink, void *ctp_ctx,
+                       mcx_sink_fn list_sink, void *list_ctx);
+int mcx_links_get_stats(const mcx_links *l, mcx_links_stats *stats);
+int mcx_links_hist(mcx_links *l, uint64_t *out);
+int mcx_links_error(const mcx_links *l, int *code, uint64_t *byte_offset);
+int mcx_links_phases(const mcx_links *l, double *ms /* [8] */);
+void mcx_links_destroy(mcx_links *l);
 
 /* Sharded build, exchange format v3 ("reads travel, not occurrences"; odd k in 29..63,
  * mcx_superk_supported(); records are mcx_superk_record_bytes(k) = 16 bytes for one-word keys, 32

@@ -5384,6 +5384,8 @@ extern "C" int mcx_records_sorted(const void *recs, uint64_t nrecs, int kmer_siz
 
 // `join`: kernels and entries (they use the sort and scan helpers above)
 #include "mcx_join.h"
+// `links`: the same
+#include "mcx_links.h"
 
 // ---------------------------------------------------------------------------
 // host-side primitives (rows A-C), same templates the kernels use

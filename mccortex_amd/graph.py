@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _build
 
-MCX_OK, MCX_ERR_ARG, MCX_ERR_NODEVICE, MCX_ERR_NOMEM, MCX_ERR_FULL, MCX_ERR_HIP, MCX_ERR_SINK = 0, -1, -2, -3, -4, -5, -6
+MCX_OK, MCX_ERR_ARG, MCX_ERR_NODEVICE, MCX_ERR_NOMEM, MCX_ERR_FULL, MCX_ERR_HIP, MCX_ERR_SINK, MCX_ERR_INVAL = 0, -1, -2, -3, -4, -5, -6, -7
 
 _LIB = None
 
@@ -29,6 +29,8 @@ SYMBOLS = [
     "mcx_graph_correct", "mcx_graph_correct_stream_dev", "mcx_graph_correct_walk_steps",
     "mcx_graph_thread", "mcx_graph_links_info", "mcx_graph_links_contig_hist", "mcx_graph_links_text", "mcx_graph_links_reset",
     "mcx_join_create", "mcx_join_configure", "mcx_join_get_stats", "mcx_join_phases", "mcx_join_buffer", "mcx_join_add_records", "mcx_join_finish", "mcx_join_destroy",
+    "mcx_links_create", "mcx_links_configure", "mcx_links_buffer", "mcx_links_add_text", "mcx_links_get_stats", "mcx_links_hist", "mcx_links_error",
+    "mcx_links_phases", "mcx_links_destroy",
 ]
 
 
@@ -160,6 +162,19 @@ class JoinStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class LinksParams(C.Structure):
+    """mcx_links_params"""
+    _fields_ = [("flags", C.c_uint32), ("distsize", C.c_uint32), ("covgsize", C.c_uint32), ("reserved", C.c_uint32),
+                ("cutoff", C.c_uint64), ("max_kmers", C.c_uint64)]
+
+
+class LinksStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("kmers_read", "kmers_with_links", "links", "link_bytes", "tree_links", "links_in")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class UnitigsArrays(C.Structure):
     """mcx_unitigs_arrays (device pointers)"""
     _fields_ = [(n, C.c_void_p) for n in ("keys", "unitig", "rank", "orient", "first", "length")]
@@ -222,6 +237,16 @@ def lib():
     L.mcx_join_phases.argtypes = [vp, C.POINTER(C.c_double)]
     L.mcx_join_destroy.argtypes = [vp]
     L.mcx_join_destroy.restype = None
+    L.mcx_links_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
+    L.mcx_links_configure.argtypes = [vp, C.c_char_p, C.c_uint64]
+    L.mcx_links_buffer.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
+    L.mcx_links_add_text.argtypes = [vp, vp, C.c_uint64, C.POINTER(LinksParams), SINK_FN, vp, SINK_FN, vp]
+    L.mcx_links_get_stats.argtypes = [vp, C.POINTER(LinksStats)]
+    L.mcx_links_hist.argtypes = [vp, u64p]
+    L.mcx_links_error.argtypes = [vp, C.POINTER(C.c_int), u64p]
+    L.mcx_links_phases.argtypes = [vp, C.POINTER(C.c_double)]
+    L.mcx_links_destroy.argtypes = [vp]
+    L.mcx_links_destroy.restype = None
     L.mcx_graph_unitig_stats.argtypes = [vp, vp]
     L.mcx_graph_clean.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(CleanStats), vp]
     L.mcx_graph_pop_bubbles.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PopStats)]
@@ -887,6 +912,83 @@ class Join:
         _check(self.L.mcx_join_finish(self.h, SINK_FN(sink), None, C.byref(st)))
         self.chunks = [len(p) if keep else p for p in parts]
         return (b"".join(parts) if keep else b""), st.as_dict()
+
+
+LINKS_CLEAN, LINKS_HIST = 1, 2
+LINKS_REFUSALS = {1: "bad_kmer_line", 2: "bad_orient", 3: "bad_number", 4: "multi_colour", 5: "bad_junction", 6: "njuncs_range",
+                  7: "njuncs_length", 8: "no_seq", 9: "no_juncpos", 10: "juncpos_count", 11: "seq_length", 12: "seq_base",
+                  13: "link_before_kmer"}
+
+
+class Links:
+    """`links` on the device: the body of a version-4 .ctp file cleaned, listed and counted (no graph, no table)."""
+
+    def __init__(self, kmer_size, device=0):
+        self.L = lib()
+        self.h = None
+        self.k = kmer_size
+        self.hist_shape = None
+        h = C.c_void_p()
+        _check(self.L.mcx_links_create(C.byref(h), kmer_size, device))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.L.mcx_links_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def configure(self, key, value):
+        _check(self.L.mcx_links_configure(self.h, key.encode(), int(value)))
+
+    def add(self, text, clean=None, hist=None, max_kmers=0, ctp=True, rows=True):
+        """text: whole k-mer blocks of a .ctp body; clean: the cut-off or None; hist: (distsize, covgsize) or None;
+        -> (.ctp bytes, list bytes).  ctp / rows = False: that text is not made (benchmarks)"""
+        text = bytes(text)
+        p = LinksParams()
+        p.flags = (LINKS_CLEAN if clean is not None else 0) | (LINKS_HIST if hist is not None else 0)
+        p.cutoff = int(clean) if clean is not None else 0
+        if hist is not None:
+            p.distsize, p.covgsize = int(hist[0]), int(hist[1])
+        p.max_kmers = int(max_kmers)
+        out, lst = [], []
+
+        def sink_to(parts):
+            def sink(_ctx, ptr, n):
+                parts.append(C.string_at(ptr, n))
+                return 0
+            return SINK_FN(sink)
+
+        none = C.cast(None, SINK_FN)
+        a, b = sink_to(out), sink_to(lst)
+        _check(self.L.mcx_links_add_text(self.h, text, len(text), C.byref(p), a if ctp else none, None, b if rows else none, None))
+        if hist is not None:
+            self.hist_shape = (int(hist[0]), int(hist[1]))
+        self.chunks = [len(x) for x in out], [len(x) for x in lst]
+        return b"".join(out), b"".join(lst)
+
+    def stats(self):
+        st = LinksStats()
+        _check(self.L.mcx_links_get_stats(self.h, C.byref(st)))
+        return st.as_dict()
+
+    def hist(self):
+        """the distsize x covgsize counters so far"""
+        a = np.zeros(self.hist_shape, dtype=np.uint64)
+        _check(self.L.mcx_links_hist(self.h, a.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return a
+
+    def error(self):
+        """after an McxError of code MCX_ERR_INVAL: (refusal name, byte offset of the first bad line in the text)"""
+        code, off = C.c_int(0), C.c_uint64(0)
+        _check(self.L.mcx_links_error(self.h, C.byref(code), C.byref(off)))
+        return LINKS_REFUSALS.get(code.value, code.value), int(off.value)
+
+    def phases(self):
+        ms = (C.c_double * 8)()
+        _check(self.L.mcx_links_phases(self.h, ms))
+        return dict(zip(("upload_ms", "lines_ms", "parse_ms", "sort_ms", "reduce_lcp_ms", "tree_ms", "written_ms", "text_ms"), [float(x) for x in ms]))
 
 
 def records_sorted(recs, kmer_size, ncols, device=0):

@@ -154,89 +154,60 @@ static int gz_sink(void *ctx, const void *data, size_t nbytes)
   return 0;
 }
 
-/* a JSON string with its quotes */
-static void put_str(gzFile gz, const char *s)
-{
-  gzputc(gz, '"');
-  for (; *s; s++) {
-    const unsigned char ch = (unsigned char)*s;
-    if (ch == '"' || ch == '\\') { gzputc(gz, '\\'); gzputc(gz, ch); }
-    else if (ch == '\n') gzputs(gz, "\\n");
-    else if (ch == '\t') gzputs(gz, "\\t");
-    else if (ch < 0x20) gzprintf(gz, "\\u%04x", ch);
-    else gzputc(gz, ch);
-  }
-  gzputc(gz, '"');
-}
-
-/* hex_rand_str (util.c): n hex digits */
-static void hex_key(char *out, size_t n)
-{
-  static bool seeded = false;
-  if (!seeded) {
-    struct timespec ts;
-    clock_gettime(CLOCK_REALTIME, &ts);
-    srandom((unsigned)ts.tv_nsec ^ (unsigned)ts.tv_sec ^ ((unsigned)getpid() << 11));
-    seeded = true;
-  }
-  for (size_t i = 0; i < n; i++) out[i] = "0123456789abcdef"[random() & 15];
-  out[n] = '\0';
-}
-
 /* gpath_save_mkhdr: the header of a .ctp file of version 4, closed by an empty line */
 static void write_header(gzFile gz, const char *out_path, int argc, char **argv, size_t kmer_size, uint64_t nkmers, const col_info *col,
                          const reads_task *tasks, const thread_opts *opts, size_t ntasks, const mcx_links_info *info, const uint64_t *hist_len,
                          const uint64_t *hist_cnt, size_t nhist)
 {
   char file_key[17], cmd_key[9], cwd[PATH_MAX + 1], abspath[PATH_MAX + 1], date[50], user[1025] = "noname";
-  hex_key(file_key, 16);
-  hex_key(cmd_key, 8);
+  ctp_hex_key(file_key, 16);
+  ctp_hex_key(cmd_key, 8);
   if (!getcwd(cwd, sizeof(cwd))) strcpy(cwd, ".");
   if (!realpath(out_path, abspath)) snprintf(abspath, sizeof(abspath), "%s", out_path);
   const time_t now = time(NULL);
   strftime(date, sizeof(date), "%Y-%m-%d %H:%M:%S", localtime(&now));
   gzputs(gz, "{\n  \"file_format\": \"ctp\",\n  \"format_version\": 4,\n  \"file_key\": ");
-  put_str(gz, file_key);
+  ctp_put_str(gz, file_key);
   gzprintf(gz, ",\n  \"graph\": {\n    \"num_colours\": 1,\n    \"kmer_size\": %zu,\n    \"num_kmers_in_graph\": %llu,\n    \"colours\": [{\n", kmer_size,
            (unsigned long long)nkmers);
   gzputs(gz, "        \"colour\": 0,\n        \"sample\": ");
-  put_str(gz, col->name ? col->name : "undefined");
+  ctp_put_str(gz, col->name ? col->name : "undefined");
   gzprintf(gz, ",\n        \"total_sequence\": %llu,\n        \"cleaned_tips\": %s,\n", (unsigned long long)col->total_sequence,
            col->cleaning.cleaned_tips ? "true" : "false");
   if (col->cleaning.cleaned_unitigs) gzprintf(gz, "        \"cleaned_unitigs\": %u\n", col->cleaning.clean_unitigs_thresh);
   else gzputs(gz, "        \"cleaned_unitigs\": false\n");
   gzputs(gz, "      }]\n  },\n  \"commands\": [{\n      \"key\": ");
-  put_str(gz, cmd_key);
+  ctp_put_str(gz, cmd_key);
   gzputs(gz, ",\n      \"cmd\": [");
-  put_str(gz, CMD_NAME);
-  for (int i = 0; i < argc; i++) { gzputs(gz, ", "); put_str(gz, argv[i]); }
+  ctp_put_str(gz, CMD_NAME);
+  for (int i = 0; i < argc; i++) { gzputs(gz, ", "); ctp_put_str(gz, argv[i]); }
   gzputs(gz, "],\n      \"cwd\": ");
-  put_str(gz, cwd);
+  ctp_put_str(gz, cwd);
   gzputs(gz, ",\n      \"out_path\": ");
-  put_str(gz, abspath);
+  ctp_put_str(gz, abspath);
   gzputs(gz, ",\n      \"out_key\": ");
-  put_str(gz, file_key);
+  ctp_put_str(gz, file_key);
   gzputs(gz, ",\n      \"date\": ");
-  put_str(gz, date);
+  ctp_put_str(gz, date);
   gzputs(gz, ",\n      \"mccortex\": \"" CMD_NAME " on libmcxgpu\",\n      \"zlib\": ");
-  put_str(gz, zlibVersion());
+  ctp_put_str(gz, zlibVersion());
   struct passwd pwd, *res = NULL;
   char pwbuf[4096];
   if (getpwuid_r(geteuid(), &pwd, pwbuf, sizeof(pwbuf), &res) == 0 && res) snprintf(user, sizeof(user), "%s", res->pw_name);
   gzputs(gz, ",\n      \"user\": ");
-  put_str(gz, user);
+  ctp_put_str(gz, user);
   struct utsname sys;
   if (uname(&sys) != -1) {
     const char *const names[5] = {"host", "os", "osrelease", "osversion", "hardware"};
     const char *const vals[5] = {sys.nodename, sys.sysname, sys.release, sys.version, sys.machine};
-    for (int i = 0; i < 5; i++) { gzprintf(gz, ",\n      \"%s\": ", names[i]); put_str(gz, vals[i]); }
+    for (int i = 0; i < 5; i++) { gzprintf(gz, ",\n      \"%s\": ", names[i]); ctp_put_str(gz, vals[i]); }
   }
   gzputs(gz, ",\n      \"prev\": [],\n      \"thread\": {\n        \"inputs\": [");
   for (size_t i = 0; i < ntasks; i++) { /* correct_aln_input_json_hdr */
     const thread_opts *o = &opts[i];
     gzputs(gz, i ? ", {\n" : "{\n");
     gzputs(gz, "            \"files\": [");
-    put_str(gz, seq_in_path(tasks[i].f1));
+    ctp_put_str(gz, seq_in_path(tasks[i].f1));
     gzprintf(gz, "],\n            \"interleaved\": false,\n            \"fq_offset\": 0,\n            \"fq_cutoff\": 0,\n            \"hp_cutoff\": 0,\n"
              "            \"matepair\": \"%s\",\n            \"frag_len_min_bp\": %u,\n            \"frag_len_max_bp\": %u,\n"
              "            \"one_way_gap_fill\": %s,\n            \"use_end_check\": %s,\n            \"max_context\": %u,\n"

@@ -188,6 +188,34 @@ void ctx_load_graph_file(struct mcx_graph *g, ctx_reader *r); /* "[GReader] N km
 void ctx_write_graph(struct mcx_graph *g, const char *out_path, size_t kmer_size, size_t ncols, const col_info *cols, bool sort_kmers);
 void ctx_dumped_status(uint64_t nkmers, size_t kmer_size, size_t ncols, size_t hdr_bytes, const char *out_path);
 
+/* ---- the JSON header of a .ctp file as text, and its body in pieces of whole k-mer blocks (ctp_hdr.c) ---- */
+struct gzFile_s;
+void ctp_put_str(struct gzFile_s *gz, const char *s); /* a JSON string with its quotes */
+void ctp_hex_key(char *out, size_t n);                /* hex_rand_str: n hex digits and a NUL */
+typedef struct { char *b; size_t len, cap; } ctp_str; /* a growing string, {NULL, 0, 0} to begin with */
+void ctp_str_add(ctp_str *s, const char *p, size_t n);
+size_t ctp_hdr_span(const char *buf, size_t n); /* bytes of the leading object; 0: not ended yet; (size_t)-1: no object */
+bool ctp_json_member(const char *obj, const char *obj_end, const char *key, const char **vbeg, const char **vend);
+bool ctp_hdr_number(const char *hdr, size_t n, const char *k1, const char *k2, uint64_t *out);
+void ctp_hdr_command(ctp_str *s, const char *cmd_key, int argc, char **argv, const char *out_path, const char *file_key, const char *prev_key);
+bool ctp_hdr_first_command_key(const char *hdr, size_t n, char *key, size_t keylen);
+char *ctp_hdr_edit(const char *hdr, size_t n, const char *file_key, const char *command, uint64_t nkmers, uint64_t npaths, uint64_t nbytes,
+                   size_t *out_len, const char **why);
+size_t ctp_cut(const char *buf, size_t n);
+typedef int (*ctp_read_fn)(void *ctx, void *dst, unsigned n); /* as gzread: bytes read, 0 at the end, < 0 on failure */
+typedef char *(*ctp_grow_fn)(void *ctx, size_t bytes);        /* a new buffer of `bytes`; the old one is gone */
+typedef struct {
+  char *buf;
+  size_t cap, fill, taken;
+  bool eof;
+  ctp_read_fn rd;
+  ctp_grow_fn grow;
+  void *rd_ctx, *grow_ctx;
+} ctp_pieces;
+void ctp_pieces_init(ctp_pieces *p, char *buf, size_t cap, ctp_read_fn rd, void *rd_ctx, ctp_grow_fn grow, void *grow_ctx);
+void ctp_pieces_preload(ctp_pieces *p, const char *data, size_t n);
+long long ctp_pieces_next(ctp_pieces *p);
+
 /* ---- commands ---- */
 int ctx_build(int argc, char **argv);
 int ctx_sort(int argc, char **argv);
@@ -202,6 +230,7 @@ int ctx_coverage(int argc, char **argv);    /* src/commands/ctx_coverage.c */
 int ctx_correct(int argc, char **argv);     /* src/commands/ctx_correct.c */
 int ctx_thread(int argc, char **argv);      /* src/commands/ctx_thread.c */
 int ctx_join(int argc, char **argv);        /* src/commands/ctx_join.c */
+int ctx_links(int argc, char **argv);       /* src/commands/ctx_links.c */
 int ctx_hashtest(int argc, char **argv);    /* src/commands/ctx_exp_hashtest.c */
 
 /* ---- sequence output of `reads` (src/basic/seqout.{h,c}): <O>.fq.gz / .fa.gz / .txt.gz, for a paired task also
