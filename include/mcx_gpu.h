@@ -624,6 +624,94 @@ enum { MCX_LINKS_SEQ = 1 }; /* add seq= and juncpos= */
 int mcx_graph_links_text(mcx_graph *g, uint32_t flags, mcx_sink_fn sink, void *ctx);
 int mcx_graph_links_reset(mcx_graph *g);
 
+/* mcx_graph_links_load_text puts the links of a .ctp onto the handle: `text` is whole k-mer blocks of a version-4,
+ * one-colour .ctp body (what mcx_links_add_text takes, cut by ctp_pieces_*).  The links join the handle's store, merged
+ * with what is there by the sort and reduce of `thread`: equal links add their counts, a count stays at 255.  A k-mer
+ * line is looked up by its canonical key (a line that holds the reverse complement turns its links round).  The
+ * reference dies on a k-mer that is not in the table (GPATH_DIE_MISSING_KMERS); here *nmissing counts them, none of the
+ * piece's links are stored and the call is MCX_ERR_INVAL.  A malformed line is MCX_ERR_INVAL too; seq= and juncpos= are
+ * optional and ignored.  *nlinks = the link lines stored.  For a handle whose links came from mcx_graph_thread,
+ * links_text, links_reset, links_load_text of those bytes gives the same links_text and the same links_info.
+ * Refusals: those of mcx_graph_thread without the one on ncols (the links are then those of the colour assembled). */
+int mcx_graph_links_load_text(mcx_graph *g, const void *text, uint64_t nbytes, uint64_t *nlinks /* or NULL */, uint64_t *nmissing /* or NULL */);
+
+/* `contigs` (src/commands/ctx_contigs.c, src/tools/assemble_contigs.c, src/graph/graph_walker.c): every seed k-mer is
+ * walked both ways by a walker that uses the links on the handle.  The graph view is that of mcx_graph_correct: union
+ * edges, in the sample iff the value word of `colour` is non-zero, an edge that names an absent k-mer counts as no edge.
+ *   Walker state: the oriented node; the held links, oldest first, as (link, pos, age); the counter links likewise; the
+ *       segments, newest first, as (in_fork, out_fork, num_nodes) (_gw_gseg_init, _gw_gseg_update, graph_walker.c:97-147:
+ *       a step at a fork, or onto a node with another previous node in the sample, opens a segment, every link ages by
+ *       one, the segments older than the oldest link go; the step adds a node to the newest).
+ *   Start (graph_walker_start): one segment of one node, then the pick-up at the start node.
+ *   Pick up (pickup_paths:151-210): only at a node in the sample; every stored link of the node with its orientation, in
+ *       store order (gpath_cmp), with pos 0 and age 0.  Counter pick-up at a previous node whose out-degree in the sample
+ *       is above 1: only links whose first base is that of the step, with pos 1, and only if they are longer than 1.
+ *   Choose (graph_walker_choose:371-515): successors over the union edges in ACGT order.  None: NOCOVG.  One: COLFWD, or
+ *       POPFWD when it is not in the sample.  Several: those in the sample; one: POPFRK_COLFWD; none: NOCOLCOVG.  Several
+ *       in the sample: no held link, or the oldest has age 0: NOLINKS; the first held link that names another base than
+ *       the oldest has the oldest's age: SPLIT_LINKS; choice_age = that link's age (0 if all agree), choice_seg = the
+ *       first segment from choice_age on with in_fork, path_gap = the nodes of the segments up to it (:474-496); with the
+ *       missing-information check, fewer bases named by held and counter links than successors: MISSING_LINKS; else
+ *       USELINKS towards the oldest link's base.  Where a held or counter link names a base that is no successor in the
+ *       sample the reference aborts (_corrupt_paths), and where no segment up to the oldest link's has in_fork it would
+ *       read past its list: HERE THE WALK STOPS WITH StopUnknown and stats.corrupt_links counts it.
+ *   Step (_graph_walker_force_jump:525-629): at a fork (POPFRK_COLFWD, USELINKS) held links that name the base taken
+ *       advance and go when they end, the others go; counter links advance while pos + 1 < len, else go; fork_count += 1.
+ *       If the new node is in the sample, its previous nodes over the union edges other than the one come from, in the
+ *       sample (db_graph_prev_nodes_with_mask), are the counter pick-ups (only with the check on); rv_fork iff there is
+ *       one.  Then the segment update, then the pick-up at the new node.
+ *   Assembly (_assemble_contig without a seed link): the buffer is the seed key forward; for dir 0, 1 (the buffer turned
+ *       round for dir 1) a clean walker starts at the buffer's last node; per step the node is appended and
+ *       wlk_steps[status] counted; on USELINKS gap_length = path_gap + k + 1, confid = conf[gap_length] (0.0 beyond the
+ *       table), max_step_gap and gap_conf[dir] *= confid are updated in that order, then StopLowStepConfidence if confid <
+ *       min_step_confid, StopLowCumulativeConfidence if gap_conf < min_cumul_confid; then the repeat rule.  Per dir
+ *       paths_held, paths_cntr and the stop cause (graphstep2assem); num_junc = the forks of both directions.
+ *   Repeat rule (repeat_walker.h:18-50): the first entry of an oriented node by a step passes (the start node is no
+ *       entry); a later one passes iff no earlier non-first entry of that node in this direction had an equal state, else
+ *       StopHitLoop and the node stays.  States are compared by a 64-bit hash of both lists: h = mix(count), then per link
+ *       mix(h ^ id), mix(h ^ (pos | len << 32)), mix(h ^ age), held then counter, mix = the finaliser of splitmix64, id =
+ *       the link's index in the store.  The reference's Bloom false positives are not reproduced.
+ *   Seeding: seeds in order -- without seed reads every key in the sample in ascending key order; with them (layout of
+ *       mcx_graph_add_reads) the reads in input order, each k bases of ACGT (else MCX_ERR_INVAL); a read that is no key
+ *       adds to seeds_not_found, one not in the sample is skipped.  MCX_CONTIGS_RESEED: every seed gives a contig.
+ *       Default: seed i gives a contig iff its k-mer is not among the nodes of a contig kept from a seed before it, else
+ *       num_reseed_abort += 1.  Only the first `ncontigs` kept contigs exist (0: no limit); later seeds add to nothing.
+ *       THE CONTIGS COME IN THAT ORDER (the reference walks its hash table with racing threads).
+ * Records go to rec_sink in contig order (whole mcx_contig_rec per call), `<bases>\n` per contig to seq_sink in the same
+ * order in consecutive ranges (len_nodes + k - 1 bases, db_nodes_print); either may be NULL.  seq_off = the contig's
+ * offset in that text.  The doubles are multiplied on the device in step order.  Nothing depends on the knobs
+ * "contigs_batch" (seeds walked per launch), "contigs_held" and "contigs_nodes" (first capacities of a walk's list and
+ * node ranges; a walk that fills one is run again with twice as much, stats.reruns counts those, MCX_ERR_NOMEM when that
+ * no longer fits), on "grid" or on the table's size.  A walk whose state never repeats on a fork-free cycle (links that no
+ * `thread` over this graph makes: one stored on a node of such a cycle is picked up again every round) grows until the
+ * call ends with MCX_ERR_NOMEM; the reference spins there.  Refusals (MCX_ERR_ARG): a graph split over devices, intersect
+ * mode, colour >= ncols, unknown flags, NaN bounds, nconf without conf. */
+enum { MCX_CONTIGS_RESEED = 1, MCX_CONTIGS_NO_MISSING_CHECK = 2 };
+typedef struct {
+  uint32_t colour, flags;
+  uint64_t ncontigs;
+  double min_step_confid, min_cumul_confid; /* < 0: off */
+  const double *conf;
+  uint64_t nconf;
+} mcx_contigs_params;
+typedef struct {
+  uint64_t seed_key[4];
+  uint64_t len_nodes, seq_off;
+  uint32_t num_junc, paths_held[2], paths_cntr[2];
+  uint64_t max_step_gap[2];
+  double gap_conf[2];
+  uint8_t stop_causes[2], outdegree_rv, outdegree_fw;
+} mcx_contig_rec;
+typedef struct {
+  uint64_t contigs, num_reseed_abort, seeds_not_found;
+  uint64_t stop_causes[9]; /* ASSEM_STOP_*: Unknown, NoCovg, PopForkNoColCovg, ForkNoPaths, ForkInPaths, MissingPaths, HitLoop, LowStep, LowCumul */
+  uint64_t wlk_steps[9];   /* GRPHWLK_*: the steps taken, by status */
+  uint64_t total_nodes, total_junc, corrupt_links, reruns;
+} mcx_contigs_stats;
+int mcx_graph_contigs(mcx_graph *g, const uint8_t *seed_bases, const uint64_t *seed_offsets /* NULL: every key */, uint64_t nseeds,
+                      const mcx_contigs_params *p, mcx_sink_fn rec_sink, void *rec_ctx, mcx_sink_fn seq_sink, void *seq_ctx,
+                      mcx_contigs_stats *stats_accum /* optional, += */);
+
 /* `inferedges`: infer_kmer_edges (src/tools/infer_edges.c) for every record of `recs` (.ctx body
  * layout, ncols == the graph's colours) against the k-mers loaded into the graph.  Each edge that some
  * colour lacks (default, --all) or that some colour has and another lacks (MCX_INFER_POP, --pop)

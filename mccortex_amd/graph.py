@@ -28,6 +28,7 @@ SYMBOLS = [
     "mcx_graph_coverage", "mcx_graph_coverage_stream_dev", "mcx_graph_coverage_text",
     "mcx_graph_correct", "mcx_graph_correct_stream_dev", "mcx_graph_correct_walk_steps",
     "mcx_graph_thread", "mcx_graph_links_info", "mcx_graph_links_contig_hist", "mcx_graph_links_text", "mcx_graph_links_reset",
+    "mcx_graph_links_load_text", "mcx_graph_contigs",
     "mcx_join_create", "mcx_join_configure", "mcx_join_get_stats", "mcx_join_phases", "mcx_join_buffer", "mcx_join_add_records", "mcx_join_finish", "mcx_join_destroy",
     "mcx_links_create", "mcx_links_configure", "mcx_links_buffer", "mcx_links_add_text", "mcx_links_get_stats", "mcx_links_hist", "mcx_links_error",
     "mcx_links_phases", "mcx_links_destroy",
@@ -144,6 +145,29 @@ class LinksInfo(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class ContigsParams(C.Structure):
+    """mcx_contigs_params"""
+    _fields_ = [("colour", C.c_uint32), ("flags", C.c_uint32), ("ncontigs", C.c_uint64), ("min_step_confid", C.c_double),
+                ("min_cumul_confid", C.c_double), ("conf", C.c_void_p), ("nconf", C.c_uint64)]
+
+
+class ContigsStats(C.Structure):
+    """mcx_contigs_stats"""
+    _fields_ = [("contigs", C.c_uint64), ("num_reseed_abort", C.c_uint64), ("seeds_not_found", C.c_uint64), ("stop_causes", C.c_uint64 * 9),
+                ("wlk_steps", C.c_uint64 * 9), ("total_nodes", C.c_uint64), ("total_junc", C.c_uint64), ("corrupt_links", C.c_uint64),
+                ("reruns", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n in ("stop_causes", "wlk_steps") else int(getattr(self, n))) for n, _ in self._fields_}
+
+
+# mcx_contig_rec
+CONTIG_REC = np.dtype([("seed_key", "<u8", 4), ("len_nodes", "<u8"), ("seq_off", "<u8"), ("num_junc", "<u4"), ("paths_held", "<u4", 2),
+                       ("paths_cntr", "<u4", 2), ("max_step_gap", "<u8", 2), ("gap_conf", "<f8", 2), ("stop_causes", "u1", 2),
+                       ("outdegree_rv", "u1"), ("outdegree_fw", "u1")], align=True)
+CONTIGS_RESEED, CONTIGS_NO_MISSING_CHECK = 1, 2
 
 
 class UnitigsStats(C.Structure):
@@ -268,6 +292,8 @@ def lib():
     L.mcx_graph_links_contig_hist.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     L.mcx_graph_links_text.argtypes = [vp, C.c_uint32, SINK_FN, vp]
     L.mcx_graph_links_reset.argtypes = [vp]
+    L.mcx_graph_links_load_text.argtypes = [vp, vp, C.c_uint64, u64p, u64p]
+    L.mcx_graph_contigs.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(ContigsParams), SINK_FN, vp, SINK_FN, vp, C.POINTER(ContigsStats)]
     L.mcx_graph_correct_walk_steps.restype = C.c_uint64
     L.mcx_graph_unitigs.argtypes = [vp, C.c_int, C.c_uint32, SINK_FN, vp, C.POINTER(UnitigsStats)]
     L.mcx_graph_unitigs_dev.argtypes = [vp, C.POINTER(UnitigsArrays), C.POINTER(UnitigsStats)]
@@ -774,6 +800,50 @@ class Graph:
     def links_reset(self):
         """forget the links and the contig histogram"""
         _check(self.L.mcx_graph_links_reset(self.h))
+
+    def links_load_text(self, text):
+        """the links of whole k-mer blocks of a version-4, one-colour .ctp body onto the handle, merged with those it keeps.
+        Returns (link lines stored, k-mers missing); raises McxError (with .nmissing set) when a k-mer is not in the graph."""
+        text = bytes(text)
+        nl, nm = C.c_uint64(0), C.c_uint64(0)
+        rc = self.L.mcx_graph_links_load_text(self.h, text, len(text), C.byref(nl), C.byref(nm))
+        if rc != MCX_OK:
+            err = McxError(rc, self.L.mcx_last_error().decode())
+            err.nmissing = int(nm.value)
+            raise err
+        return int(nl.value), int(nm.value)
+
+    def contigs(self, conf=(), colour=0, seeds=None, reseed=False, missing_check=True, ncontigs=0, min_step_confid=-1.0,
+                min_cumul_confid=-1.0, stats=None, want_seq=True):
+        """`contigs` (ctx_contigs.c): every seed walked both ways with the links on the handle.  seeds: None = every key of
+        the sample in key order, else a list of k-base strings.  conf: the confidence table indexed by gap length.
+        Returns (records as a CONTIG_REC array, the sequences as bytes `<bases>\n` per contig, ContigsStats)."""
+        conf = np.ascontiguousarray(conf, dtype=np.float64)
+        bases = offsets = None
+        nseeds = 0
+        if seeds is not None:
+            bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seeds]
+            nseeds = len(bs)
+            bases = np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8).copy()
+            offsets = np.cumsum([0] + [len(b) for b in bs]).astype(np.uint64)
+        recs, seq = [], []
+
+        def rec_sink(_ctx, ptr, n):
+            recs.append(C.string_at(ptr, n))
+            return 0
+
+        def seq_sink(_ctx, ptr, n):
+            seq.append(C.string_at(ptr, n))
+            return 0
+
+        st = stats if stats is not None else ContigsStats()
+        flags = (CONTIGS_RESEED if reseed else 0) | (0 if missing_check else CONTIGS_NO_MISSING_CHECK)
+        prm = ContigsParams(int(colour), flags, int(ncontigs), float(min_step_confid), float(min_cumul_confid),
+                            conf.ctypes.data_as(C.c_void_p) if len(conf) else None, len(conf))
+        a, b = SINK_FN(rec_sink), SINK_FN(seq_sink)
+        _check(self.L.mcx_graph_contigs(self.h, _ptr(bases), _ptr(offsets), nseeds, C.byref(prm), a, None, b if want_seq else C.cast(None, SINK_FN), None,
+                                        C.byref(st)))
+        return np.frombuffer(b"".join(recs), dtype=CONTIG_REC), b"".join(seq), st
 
     def subgraph(self, seeds, dist=0, invert=False, unitigs=False):
         """`subgraph` (ctx_subgraph.c): keep the k-mers within `dist` edges of the k-mers of `seeds` (a list of str or
