@@ -712,6 +712,63 @@ int mcx_graph_contigs(mcx_graph *g, const uint8_t *seed_bases, const uint64_t *s
                       const mcx_contigs_params *p, mcx_sink_fn rec_sink, void *rec_ctx, mcx_sink_fn seq_sink, void *seq_ctx,
                       mcx_contigs_stats *stats_accum /* optional, += */);
 
+/* `bubbles` (src/commands/ctx_bubbles.c, src/tools/bubble_caller.c, src/graph/graph_crawler.c, src/graph/graph_cache.c)
+ * WITHOUT LINK FILES: where the colours of a joined graph differ.  The graph view is that of mcx_graph_correct: union
+ * edges, a k-mer is in a sample iff its value word in that colour is non-zero, an edge that names an absent k-mer counts
+ * as no edge.  Unitigs are those of mcx_graph_unitig_stats, normalised as mcx_graph_unitigs prints them.
+ *   Forks (bubble_caller_node): an oriented node with more than one successor that is a key.  FORKS ARE TAKEN IN
+ *       ASCENDING KEY ORDER, FORWARD BEFORE REVERSE, and the ids `call<id>` count up from 0 in output order (the
+ *       reference walks its hash table with racing threads).
+ *   Paths (find_bubbles, graph_crawler_load_path_limit): colours ascending that hold the fork node; per colour every
+ *       successor in ACGT order that is in the colour starts a path.  A path is a list of steps (unitig, orientation:
+ *       FORWARD iff entered at the normalised unitig's first node).  After a step the unitig's k-mers are added to the
+ *       path's total; at or above max_allele the path ends (the step stays).  Else the successors of the unitig's far
+ *       end (graph_walker_choose without links): none: NOCOVG; one: go, in the colour or not (POPFWD); several of which
+ *       one is in the colour: go there (POPFRK_COLFWD); none in the colour: NOCOLCOVG; several in the colour: NOLINKS.
+ *       Repeat rule (repeat_walker.h:18-50; the state never changes without links): the first and second entry of an
+ *       oriented node by a step of the path pass (the path's first node is no entry), the third ends the path without
+ *       a step.  The reference's Bloom false positives are not reproduced.
+ *   Cache (graph_cache_new_step): per fork the unitigs get local ids in the order they are first stepped on, over the
+ *       paths in the order above; the steps on a unitig form a list, newest first.
+ *   Candidates (write_bubbles_to_file, find_bubbles_ending_with): the local unitigs in id order; for each its FORWARD
+ *       steps, then its REVERSE steps.  stats.candidates counts the lists of two steps or more.
+ *   Filters (filter_bubbles), in order: graph_cache_is_3p_flank (the paths' first steps not all equal, the steps before
+ *       the candidate not all equal, a missing one differs); graph_cache_remove_dupes (sorted by graph_cache_steps_cmp
+ *       over the words local id << 1 | orientation up to and including the step, then the length; one step per equal
+ *       run; fewer than 2: no call); remove_haploid_paths (the swap-with-last loop; a path is in haploid colour r when
+ *       every k-mer of every unitig up to and including the end step is; fewer than 2: haploid_dropped += 1); unless
+ *       MCX_BUBBLES_KEEP_SERIAL paths_all_share_unitig (the words of the steps before the end step are counted over all
+ *       paths, a word met twice counts twice; a count equal to the number of paths: serial_dropped += 1, no call).
+ *   Text (print_bubble): `>bubble.call<id>.5pflank kmers=<n>\n<first k-mer, then a base per further k-mer>\n`
+ *       `>bubble.call<id>.3pflank kmers=<n>\n<a base per k-mer>\n` then per branch i `>bubble.call<id>.branch.<i>
+ *       kmers=<n>\n<a base per k-mer>\n` and a blank line.  5' flank: db_unitig_extend from the reversed fork node, at
+ *       most max_flank k-mers, turned round (it ends at the fork node).  3' flank: the whole unitig of the end step in
+ *       the step's orientation.  Branch i: the nodes of path i before the end step, in the order the filters left.
+ * One mcx_bubble_rec per call goes to rec_sink in output order, the text to text_sink in consecutive pieces of at most
+ * "bubbles_chunk" bytes (a seam may fall anywhere); either may be NULL.  text_off = the call's offset in that text;
+ * fork_key holds the key's words, most significant first.  Nothing in the records, the text or the stats depends on the
+ * knobs "bubbles_batch" (fork k-mers per launch round), "bubbles_chunk", "grid" or on the table's size.
+ * Refusals (MCX_ERR_ARG): a graph split over devices, intersect mode, max_allele == 0 or max_flank == 0, a haploid
+ * colour >= ncols, more than 64 haploid colours, unknown flags, 4 x ncols x max_allele >= 2^31.  The decomposition is
+ * reused when it still describes the table and made otherwise (the refusals of mcx_graph_clean). */
+enum { MCX_BUBBLES_KEEP_SERIAL = 1 };
+typedef struct {
+  uint32_t max_allele, max_flank, flags, nhaploid;
+  const uint32_t *haploid;
+} mcx_bubbles_params;
+typedef struct {
+  uint64_t fork_key[4];
+  uint64_t text_off, text_len;
+  uint32_t fork_orient, num_branches, flank5p_kmers, flank3p_kmers;
+} mcx_bubble_rec;
+typedef struct {
+  uint64_t forks, paths, steps;
+  uint64_t stop_limit, stop_nocovg, stop_nocolcovg, stop_nolinks, stop_repeat;
+  uint64_t candidates, bubbles, branches, haploid_dropped, serial_dropped;
+} mcx_bubbles_stats;
+int mcx_graph_bubbles(mcx_graph *g, const mcx_bubbles_params *p, mcx_sink_fn rec_sink, void *rec_ctx, mcx_sink_fn text_sink, void *text_ctx,
+                      mcx_bubbles_stats *stats_accum /* optional, += */);
+
 /* `inferedges`: infer_kmer_edges (src/tools/infer_edges.c) for every record of `recs` (.ctx body
  * layout, ncols == the graph's colours) against the k-mers loaded into the graph.  Each edge that some
  * colour lacks (default, --all) or that some colour has and another lacks (MCX_INFER_POP, --pop)

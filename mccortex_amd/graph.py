@@ -28,7 +28,7 @@ SYMBOLS = [
     "mcx_graph_coverage", "mcx_graph_coverage_stream_dev", "mcx_graph_coverage_text",
     "mcx_graph_correct", "mcx_graph_correct_stream_dev", "mcx_graph_correct_walk_steps",
     "mcx_graph_thread", "mcx_graph_links_info", "mcx_graph_links_contig_hist", "mcx_graph_links_text", "mcx_graph_links_reset",
-    "mcx_graph_links_load_text", "mcx_graph_contigs",
+    "mcx_graph_links_load_text", "mcx_graph_contigs", "mcx_graph_bubbles",
     "mcx_join_create", "mcx_join_configure", "mcx_join_get_stats", "mcx_join_phases", "mcx_join_buffer", "mcx_join_add_records", "mcx_join_finish", "mcx_join_destroy",
     "mcx_links_create", "mcx_links_configure", "mcx_links_buffer", "mcx_links_add_text", "mcx_links_get_stats", "mcx_links_hist", "mcx_links_error",
     "mcx_links_phases", "mcx_links_destroy",
@@ -170,6 +170,26 @@ CONTIG_REC = np.dtype([("seed_key", "<u8", 4), ("len_nodes", "<u8"), ("seq_off",
 CONTIGS_RESEED, CONTIGS_NO_MISSING_CHECK = 1, 2
 
 
+class BubblesParams(C.Structure):
+    """mcx_bubbles_params"""
+    _fields_ = [("max_allele", C.c_uint32), ("max_flank", C.c_uint32), ("flags", C.c_uint32), ("nhaploid", C.c_uint32), ("haploid", C.c_void_p)]
+
+
+class BubblesStats(C.Structure):
+    """mcx_bubbles_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("forks", "paths", "steps", "stop_limit", "stop_nocovg", "stop_nocolcovg", "stop_nolinks", "stop_repeat",
+                                          "candidates", "bubbles", "branches", "haploid_dropped", "serial_dropped")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+# mcx_bubble_rec
+BUBBLE_REC = np.dtype([("fork_key", "<u8", 4), ("text_off", "<u8"), ("text_len", "<u8"), ("fork_orient", "<u4"), ("num_branches", "<u4"),
+                       ("flank5p_kmers", "<u4"), ("flank3p_kmers", "<u4")], align=True)
+BUBBLES_KEEP_SERIAL = 1
+
+
 class UnitigsStats(C.Structure):
     """mcx_unitigs_stats"""
     _fields_ = [(n, C.c_uint64) for n in ("num_unitigs", "num_kmers", "num_bytes", "num_cycles")]
@@ -294,6 +314,7 @@ def lib():
     L.mcx_graph_links_reset.argtypes = [vp]
     L.mcx_graph_links_load_text.argtypes = [vp, vp, C.c_uint64, u64p, u64p]
     L.mcx_graph_contigs.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(ContigsParams), SINK_FN, vp, SINK_FN, vp, C.POINTER(ContigsStats)]
+    L.mcx_graph_bubbles.argtypes = [vp, C.POINTER(BubblesParams), SINK_FN, vp, SINK_FN, vp, C.POINTER(BubblesStats)]
     L.mcx_graph_correct_walk_steps.restype = C.c_uint64
     L.mcx_graph_unitigs.argtypes = [vp, C.c_int, C.c_uint32, SINK_FN, vp, C.POINTER(UnitigsStats)]
     L.mcx_graph_unitigs_dev.argtypes = [vp, C.POINTER(UnitigsArrays), C.POINTER(UnitigsStats)]
@@ -844,6 +865,28 @@ class Graph:
         _check(self.L.mcx_graph_contigs(self.h, _ptr(bases), _ptr(offsets), nseeds, C.byref(prm), a, None, b if want_seq else C.cast(None, SINK_FN), None,
                                         C.byref(st)))
         return np.frombuffer(b"".join(recs), dtype=CONTIG_REC), b"".join(seq), st
+
+    def bubbles(self, max_allele=2000, max_flank=500, haploid=(), keep_serial=False, stats=None):
+        """`bubbles` (ctx_bubbles.c without link files): the calls of every fork of the multi-colour graph, forks in ascending
+        key order.  haploid: colours that hold one allele only; keep_serial: skip the serial-bubble filter (-S).  stats: a
+        BubblesStats that the call adds to.  Returns (records as a BUBBLE_REC array, the text of the calls as bytes)."""
+        hap = np.ascontiguousarray(list(haploid), dtype=np.uint32)
+        recs, text = [], []
+
+        def rec_sink(_ctx, ptr, n):
+            recs.append(C.string_at(ptr, n))
+            return 0
+
+        def text_sink(_ctx, ptr, n):
+            text.append(C.string_at(ptr, n))
+            return 0
+
+        st = stats if stats is not None else BubblesStats()
+        prm = BubblesParams(int(max_allele), int(max_flank), BUBBLES_KEEP_SERIAL if keep_serial else 0, len(hap),
+                            hap.ctypes.data_as(C.c_void_p) if len(hap) else None)
+        a, b = SINK_FN(rec_sink), SINK_FN(text_sink)
+        _check(self.L.mcx_graph_bubbles(self.h, C.byref(prm), a, None, b, None, C.byref(st)))
+        return np.frombuffer(b"".join(recs), dtype=BUBBLE_REC), b"".join(text)
 
     def subgraph(self, seeds, dist=0, invert=False, unitigs=False):
         """`subgraph` (ctx_subgraph.c): keep the k-mers within `dist` edges of the k-mers of `seeds` (a list of str or
