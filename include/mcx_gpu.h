@@ -769,6 +769,78 @@ typedef struct {
 int mcx_graph_bubbles(mcx_graph *g, const mcx_bubbles_params *p, mcx_sink_fn rec_sink, void *rec_ctx, mcx_sink_fn text_sink, void *text_ctx,
                       mcx_bubbles_stats *stats_accum /* optional, += */);
 
+/* `breakpoints` (src/commands/ctx_breakpoints.c, src/tools/breakpoint_caller.c, src/graph/kmer_occur.{c,h},
+ * src/graph/graph_crawler.c) WITHOUT LINK FILES: where the samples differ from an assembled reference genome, with
+ * reference coordinates.  The graph view is that of mcx_graph_bubbles.  The reference colour is the handle's last
+ * colour, ncols - 1; chromosome c is ref_bases[ref_offsets[c] .. ref_offsets[c + 1]) (ASCII, any case) and prints as
+ * names[name_off[c] .. name_off[c + 1]) (already cleaned by the caller).
+ *   Reference (kograph_create with add_missing_kmers, add_ref_seq_to_graph_mt): every maximal ACGT run of at least k
+ *       bases goes into the last colour through mcx_graph_add_reads: coverage + 1 per occurrence, the edges between
+ *       consecutive k-mers.  MCX_BREAKPOINTS_NO_REF_EDGES (breakpoint_caller.c:625-626): coverage only, no edge bits.
+ *       MCX_BREAKPOINTS_REF_LOADED skips this: a second call on the same handle with other limits.
+ *       MCX_BREAKPOINTS_LOAD_ONLY does this and returns (stats: ref_added alone): a host that has to print the k-mer count
+ *       with the genome in ahead of the calls loads first and calls with REF_LOADED then (not both flags in one call).
+ *   Occurrences (KOGraph): per key its (chrom, offset, orient of the key relative to the genome) for every start position
+ *       of the genome whose k-mer is a key, ordered by (chrom, offset); offsets run on across non-ACGT bytes.
+ *   Breaks (breakpoint_caller_node, follow_break): an oriented node whose key occurs in the genome, with one of its
+ *       successors (keys only) that does not.  BREAKS ARE TAKEN IN ASCENDING KEY ORDER, FORWARD BEFORE REVERSE,
+ *       SUCCESSORS IN ACGT ORDER, and the ids `call<id>` count up from 0 in output order (difference 1: the reference
+ *       walks its hash table with racing threads).
+ *   Walks (graph_crawler_load_path without links): the walker and the repeat rule of mcx_graph_bubbles; a step is the
+ *       unitig that db_unitig_extend makes forward from the entered node.  After every step the run set is extended
+ *       over the step's nodes in path orientation (kograph_filter_extend, korun_extend): the sorted active runs are
+ *       scanned against the k-mer's occurrences with the reference's two pointers; strand = + iff the occurrence's
+ *       orient equals the node's; a run continues iff last + 1 (strand +) or last - 1 (strand -) == offset, the sign
+ *       taken from the occurrence; an occurrence that extends no run starts one at the node's index; an unextended run
+ *       of MORE THAN min_ref k-mers moves to the ended set, a shorter one is dropped.  The walk goes on iff
+ *       min qoffset(active) <= min qoffset(ended) and (max_ref == 0 or the longest run < max_ref) and, for a 5' flank,
+ *       the active set is not empty (gcrawler_stop_at_ref_covg).  DIFFERENCE 3: the lengths of ended runs are taken
+ *       from the ended runs (the reference reads koruns->b[i] while it loops over koruns_ended).  At the end the
+ *       path's runs are the ended ones and the active ones of AT LEAST min_ref k-mers (gcrawler_finish_ref_covg).
+ *   Per break: the 5' flank is walked from the reversed fork node in every colour (the reference colour included) that
+ *       holds both nodes; walks that are node-for-node equal merge (graph_crawler_fetch).  A merged flank is reversed
+ *       (koruns_reverse, nodes reverse-complemented), its runs sorted by (qoffset, chrom, first, last); without a run it
+ *       is dropped.  Otherwise the allele is walked forward from the non-reference successor in each colour of the
+ *       flank's set and merged likewise; a merged allele without a run is no call (process_contig).  DIFFERENCE 2: MERGED
+ *       FLANKS AND MERGED ALLELES ARE ORDERED BY THEIR SMALLEST COLOUR, colours ascending inside a set (the reference
+ *       orders them by cache-local unitig ids).
+ *   Text (process_contig): flank3pidx = the qoffset of the allele's first sorted run, extra = min(k - 1, flank3pidx),
+ *       path_kmers = flank3pidx - extra, kmer3poffset = k - 1 - extra;
+ *       `>brkpnt.call<id>.5pflank chr=<runs>\n<first k-mer, then a base per further k-mer>\n`
+ *       `>brkpnt.call<id>.3pflank chr=<runs>\n<a base per node from path_kmers on>\n`
+ *       `>brkpnt.call<id>.path cols=<c0,c1,..>\n<a base per node before path_kmers>\n\n`; a run prints as korun_gzprint
+ *       does: name:start-end:strand:offset, 1-based, with (first_kmer_idx, kmer_offset) = (0, 0) for the 5' flank and
+ *       (flank3pidx, kmer3poffset) for the 3' flank.
+ *   (Difference 4 is the command's: its header gives the real -R as max_ref_flank_kmers.)
+ * One mcx_breakpoint_rec per call goes to rec_sink in output order, the text to text_sink in consecutive pieces of at
+ * most "breakpoints_chunk" bytes (a seam may fall anywhere); either may be NULL.  Nothing in the records, the text or
+ * the stats (but `reruns`) depends on the knobs "breakpoints_batch" (break k-mers per launch round), "breakpoints_chunk",
+ * "breakpoints_runs" (runs a walk holds at a time before the batch is walked again with twice the room: reruns counts
+ * the walks that outgrew theirs), "grid" or on the table's size.  stop_bound counts walks that reached the hard cap of
+ * 4 n + 4 nodes for n k-mers, which the repeat rule keeps them from: always 0.
+ * Refusals (MCX_ERR_ARG): a graph split over devices, intersect mode, ncols < 2, nchroms == 0 or > 2^30, a chromosome
+ * longer than 2^32, min_ref == 0, max_ref != 0 && min_ref > max_ref, unknown flags; the refusals of mcx_graph_clean. */
+enum { MCX_BREAKPOINTS_NO_REF_EDGES = 1, MCX_BREAKPOINTS_REF_LOADED = 2, MCX_BREAKPOINTS_LOAD_ONLY = 4 };
+typedef struct {
+  uint32_t min_ref, max_ref /* 0: no limit */, flags;
+} mcx_breakpoints_params;
+typedef struct {
+  uint64_t fork_key[4];
+  uint64_t text_off, text_len;
+  uint32_t fork_orient, succ_base, num_cols, path_kmers;
+  uint32_t flank5p_kmers, flank3p_kmers, flank5p_runs, flank3p_runs;
+} mcx_breakpoint_rec;
+typedef struct {
+  uint64_t occurrences, ref_keys, ref_added;
+  uint64_t breaks, flank_walks, flanks, flanks_norun, allele_walks, alleles, alleles_norun, calls;
+  uint64_t steps, runs_started, runs_ended;
+  uint64_t stop_runs, stop_maxref, stop_flank, stop_nocovg, stop_nocolcovg, stop_nolinks, stop_repeat, stop_bound;
+  uint64_t reruns;
+} mcx_breakpoints_stats;
+int mcx_graph_breakpoints(mcx_graph *g, const uint8_t *ref_bases, const uint64_t *ref_offsets, uint64_t nchroms, const char *names,
+                          const uint64_t *name_off, const mcx_breakpoints_params *p, mcx_sink_fn rec_sink, void *rec_ctx,
+                          mcx_sink_fn text_sink, void *text_ctx, mcx_breakpoints_stats *stats_accum /* optional, += */);
+
 /* `inferedges`: infer_kmer_edges (src/tools/infer_edges.c) for every record of `recs` (.ctx body
  * layout, ncols == the graph's colours) against the k-mers loaded into the graph.  Each edge that some
  * colour lacks (default, --all) or that some colour has and another lacks (MCX_INFER_POP, --pop)

@@ -312,6 +312,7 @@ struct mcx_graph {
   struct ThreadStore *links = nullptr;     // thread: the links generated so far and the contig histogram (mcx_thread.h)
   uint64_t contigs_batch = 0, contigs_held = 0, contigs_nodes = 0;  // contigs: seeds per launch, first capacities of a walk's ranges (0 = default)
   uint64_t bubbles_batch = 0, bubbles_chunk = 0;  // bubbles: fork k-mers per launch round, text bytes per sink call (0 = default)
+  uint64_t breakpoints_batch = 0, breakpoints_chunk = 0, breakpoints_runs = 0;  // breakpoints: break k-mers per launch round, text bytes per sink call, runs a walk holds at first (0 = default)
   uint64_t reads_chunk = 0;                // test knob: stream bytes per chunk of mcx_graph_reads_touch and of coverage_batch (0 = what a staging buffer holds)
 };
 
@@ -1534,6 +1535,9 @@ extern "C" int mcx_graph_configure(mcx_graph *g, const char *key, uint64_t value
   if (!strcmp(key, "contigs_nodes")) { g->contigs_nodes = value; return MCX_OK; }
   if (!strcmp(key, "bubbles_batch")) { g->bubbles_batch = value; return MCX_OK; }  // bubbles: no output depends on these two
   if (!strcmp(key, "bubbles_chunk")) { g->bubbles_chunk = value; return MCX_OK; }
+  if (!strcmp(key, "breakpoints_batch")) { g->breakpoints_batch = value; return MCX_OK; }  // breakpoints: no output depends on these three
+  if (!strcmp(key, "breakpoints_chunk")) { g->breakpoints_chunk = value; return MCX_OK; }
+  if (!strcmp(key, "breakpoints_runs")) { g->breakpoints_runs = value; return MCX_OK; }
   if (!strcmp(key, "subgraph_narrow")) { g->subgraph_narrow = (uint32_t)std::min<uint64_t>(value, (uint64_t)kSgBlock); return MCX_OK; }
   if (!strcmp(key, "grid_stream")) { g->grid_stream = (int)value; return MCX_OK; }
   if (!strcmp(key, "grid_split")) { g->grid_split = (int)value; return MCX_OK; }
@@ -5397,6 +5401,8 @@ extern "C" int mcx_records_sorted(const void *recs, uint64_t nrecs, int kmer_siz
 #include "mcx_contigs.h"
 // `bubbles`: the decomposition of `clean`, the passes A and B of `unitigs`
 #include "mcx_bubbles.h"
+// `breakpoints`: the walker and the text helpers of `bubbles`, the ids of `clean`
+#include "mcx_breakpoints.h"
 
 // ---------------------------------------------------------------------------
 // host-side primitives (rows A-C), same templates the kernels use

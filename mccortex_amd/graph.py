@@ -28,7 +28,7 @@ SYMBOLS = [
     "mcx_graph_coverage", "mcx_graph_coverage_stream_dev", "mcx_graph_coverage_text",
     "mcx_graph_correct", "mcx_graph_correct_stream_dev", "mcx_graph_correct_walk_steps",
     "mcx_graph_thread", "mcx_graph_links_info", "mcx_graph_links_contig_hist", "mcx_graph_links_text", "mcx_graph_links_reset",
-    "mcx_graph_links_load_text", "mcx_graph_contigs", "mcx_graph_bubbles",
+    "mcx_graph_links_load_text", "mcx_graph_contigs", "mcx_graph_bubbles", "mcx_graph_breakpoints",
     "mcx_join_create", "mcx_join_configure", "mcx_join_get_stats", "mcx_join_phases", "mcx_join_buffer", "mcx_join_add_records", "mcx_join_finish", "mcx_join_destroy",
     "mcx_links_create", "mcx_links_configure", "mcx_links_buffer", "mcx_links_add_text", "mcx_links_get_stats", "mcx_links_hist", "mcx_links_error",
     "mcx_links_phases", "mcx_links_destroy",
@@ -190,6 +190,28 @@ BUBBLE_REC = np.dtype([("fork_key", "<u8", 4), ("text_off", "<u8"), ("text_len",
 BUBBLES_KEEP_SERIAL = 1
 
 
+class BreakpointsParams(C.Structure):
+    """mcx_breakpoints_params"""
+    _fields_ = [("min_ref", C.c_uint32), ("max_ref", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class BreakpointsStats(C.Structure):
+    """mcx_breakpoints_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("occurrences", "ref_keys", "ref_added", "breaks", "flank_walks", "flanks", "flanks_norun", "allele_walks",
+                                          "alleles", "alleles_norun", "calls", "steps", "runs_started", "runs_ended", "stop_runs", "stop_maxref",
+                                          "stop_flank", "stop_nocovg", "stop_nocolcovg", "stop_nolinks", "stop_repeat", "stop_bound", "reruns")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+# mcx_breakpoint_rec
+BREAKPOINT_REC = np.dtype([("fork_key", "<u8", 4), ("text_off", "<u8"), ("text_len", "<u8"), ("fork_orient", "<u4"), ("succ_base", "<u4"),
+                           ("num_cols", "<u4"), ("path_kmers", "<u4"), ("flank5p_kmers", "<u4"), ("flank3p_kmers", "<u4"), ("flank5p_runs", "<u4"),
+                           ("flank3p_runs", "<u4")], align=True)
+BREAKPOINTS_NO_REF_EDGES, BREAKPOINTS_REF_LOADED, BREAKPOINTS_LOAD_ONLY = 1, 2, 4
+
+
 class UnitigsStats(C.Structure):
     """mcx_unitigs_stats"""
     _fields_ = [(n, C.c_uint64) for n in ("num_unitigs", "num_kmers", "num_bytes", "num_cycles")]
@@ -315,6 +337,7 @@ def lib():
     L.mcx_graph_links_load_text.argtypes = [vp, vp, C.c_uint64, u64p, u64p]
     L.mcx_graph_contigs.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(ContigsParams), SINK_FN, vp, SINK_FN, vp, C.POINTER(ContigsStats)]
     L.mcx_graph_bubbles.argtypes = [vp, C.POINTER(BubblesParams), SINK_FN, vp, SINK_FN, vp, C.POINTER(BubblesStats)]
+    L.mcx_graph_breakpoints.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(BreakpointsParams), SINK_FN, vp, SINK_FN, vp, C.POINTER(BreakpointsStats)]
     L.mcx_graph_correct_walk_steps.restype = C.c_uint64
     L.mcx_graph_unitigs.argtypes = [vp, C.c_int, C.c_uint32, SINK_FN, vp, C.POINTER(UnitigsStats)]
     L.mcx_graph_unitigs_dev.argtypes = [vp, C.POINTER(UnitigsArrays), C.POINTER(UnitigsStats)]
@@ -887,6 +910,39 @@ class Graph:
         a, b = SINK_FN(rec_sink), SINK_FN(text_sink)
         _check(self.L.mcx_graph_bubbles(self.h, C.byref(prm), a, None, b, None, C.byref(st)))
         return np.frombuffer(b"".join(recs), dtype=BUBBLE_REC), b"".join(text)
+
+    def breakpoints(self, ref_seqs, names, min_ref=5, max_ref=1000, ref_edges=True, ref_loaded=False, stats=None, load_only=False):
+        """`breakpoints` (ctx_breakpoints.c without link files): where the samples differ from the reference genome `ref_seqs`
+        (a list of str or bytes; `names` as they print, already cleaned), which goes into the graph's last colour.  ref_edges
+        False: the genome's k-mers enter without edges (-E); ref_loaded: the genome is in the graph already (a second call
+        with other limits); load_only: the genome goes in and nothing else happens.  stats: a BreakpointsStats that the call adds to.  Returns (records as a BREAKPOINT_REC array,
+        the text of the calls as bytes)."""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in ref_seqs]
+        nms = [s.encode() if isinstance(s, str) else bytes(s) for s in names]
+        if len(seqs) != len(nms):
+            raise ValueError("a name per reference sequence")
+        offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(s) for s in seqs])
+        noff = np.zeros(len(nms) + 1, dtype=np.uint64)
+        noff[1:] = np.cumsum([len(s) for s in nms])
+        bases = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
+        nbuf = np.frombuffer(b"".join(nms) + b"\0", dtype=np.uint8)
+        recs, text = [], []
+
+        def rec_sink(_ctx, ptr, n):
+            recs.append(C.string_at(ptr, n))
+            return 0
+
+        def text_sink(_ctx, ptr, n):
+            text.append(C.string_at(ptr, n))
+            return 0
+
+        st = stats if stats is not None else BreakpointsStats()
+        prm = BreakpointsParams(int(min_ref), int(max_ref), (0 if ref_edges else BREAKPOINTS_NO_REF_EDGES) | (BREAKPOINTS_REF_LOADED if ref_loaded else 0)
+                                | (BREAKPOINTS_LOAD_ONLY if load_only else 0))
+        a, b = SINK_FN(rec_sink), SINK_FN(text_sink)
+        _check(self.L.mcx_graph_breakpoints(self.h, _ptr(bases), _ptr(offs), len(seqs), _ptr(nbuf), _ptr(noff), C.byref(prm), a, None, b, None, C.byref(st)))
+        return np.frombuffer(b"".join(recs), dtype=BREAKPOINT_REC), b"".join(text)
 
     def subgraph(self, seeds, dist=0, invert=False, unitigs=False):
         """`subgraph` (ctx_subgraph.c): keep the k-mers within `dist` edges of the k-mers of `seeds` (a list of str or

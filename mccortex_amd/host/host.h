@@ -233,6 +233,7 @@ int ctx_join(int argc, char **argv);        /* src/commands/ctx_join.c */
 int ctx_links(int argc, char **argv);       /* src/commands/ctx_links.c */
 int ctx_contigs(int argc, char **argv);     /* src/commands/ctx_contigs.c */
 int ctx_bubbles(int argc, char **argv);     /* src/commands/ctx_bubbles.c */
+int ctx_breakpoints(int argc, char **argv); /* src/commands/ctx_breakpoints.c */
 int ctx_hashtest(int argc, char **argv);    /* src/commands/ctx_exp_hashtest.c */
 
 /* ---- sequence output of `reads` (src/basic/seqout.{h,c}): <O>.fq.gz / .fa.gz / .txt.gz, for a paired task also

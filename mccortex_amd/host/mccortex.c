@@ -71,6 +71,7 @@ int main(int argc, char **argv)
   else if (!strcmp(argv[1], "links")) func = ctx_links; /* (as `coverage`: not in the pinned texts) */
   else if (!strcmp(argv[1], "contigs")) func = ctx_contigs; /* (as `coverage`: not in the pinned texts) */
   else if (!strcmp(argv[1], "bubbles")) func = ctx_bubbles; /* (as `coverage`: not in the pinned texts) */
+  else if (!strcmp(argv[1], "breakpoints")) func = ctx_breakpoints; /* (the same) */
   else if (!strcmp(argv[1], "hashtest")) func = ctx_hashtest;
   if (!func) {
     fprintf(stderr, "%s: command '%s' is not part of this build (build, sort, index, clean, inferedges, popbubbles, subgraph, unitigs, reads and hashtest are)\n\n", CMD_NAME, argv[1]);
