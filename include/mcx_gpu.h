@@ -986,7 +986,8 @@ enum {
   MCX_LINKS_JUNCPOS_COUNT = 10,   /* juncpos is no list of njuncs numbers */
   MCX_LINKS_SEQ_LENGTH = 11,      /* strlen(seq) != k + juncpos[last] + 1 */
   MCX_LINKS_SEQ_BASE = 12,        /* seq[k + juncpos[i]] != juncs[i] */
-  MCX_LINKS_LINK_BEFORE_KMER = 13 /* a link line before any k-mer line */
+  MCX_LINKS_LINK_BEFORE_KMER = 13,/* a link line before any k-mer line */
+  MCX_LINKS_COUNT_COLUMNS = 14    /* mcx_pjoin_add_text: the count column has not as many numbers as the file has colours */
 };
 typedef struct { uint32_t flags, distsize, covgsize, reserved; uint64_t cutoff, max_kmers; } mcx_links_params;
 typedef struct { uint64_t kmers_read, kmers_with_links, links, link_bytes, tree_links, links_in; } mcx_links_stats;
@@ -1000,6 +1001,48 @@ int mcx_links_hist(mcx_links *l, uint64_t *out);
 int mcx_links_error(const mcx_links *l, int *code, uint64_t *byte_offset);
 int mcx_links_phases(const mcx_links *l, double *ms /* [8] */);
 void mcx_links_destroy(mcx_links *l);
+
+/* `pjoin` (src/commands/ctx_pjoin.c, src/graph_paths/gpath_reader.c, src/paths/gpath_subset.c): the bodies of version-4
+ * .ctp files merged into one, a colour per file or several files into one colour.  No graph handle and no hash table:
+ * the links of all files are sorted by (k-mer as written, orientation, junction string) and every run of equal links is
+ * reduced to one link whose count per colour is min(255, the sum over its lines) (mcx_pjoin.h).  A prefix and its
+ * extension are different links; seq= and juncpos= are not read.
+ *   mcx_pjoin_create      kmer_size: the k of the files (odd, 3..127); out_ncols: colours of the output.
+ *   mcx_pjoin_configure   test knobs, the answers must not change with them: "grid" (at most n blocks per launch, 0 =
+ *       8 per compute unit), "out_chunk" (bytes of text per sink call, 0 = 64 MiB), "compact" (1 = the store is reduced to
+ *       its unique links after every add), "max_bytes" (the ceiling of the store's records, junction words and counts,
+ *       0 = what the device has free; a full store compacts once before an add answers MCX_ERR_NOMEM).
+ *   mcx_pjoin_buffer      pinned host memory of `bytes` bytes owned by the handle (one at a time; freed by the next call
+ *       and by destroy).
+ *   mcx_pjoin_add_text    `text`: lines of the body of a file with src_ncols colours (`<kmer> <n>` lines, each followed by
+ *       its `<F|R> <njuncs> <c0,..> <juncs> [tags]` lines; comment and empty lines anywhere), ending with a newline, less
+ *       than 2 GB.  filter: nfilter pairs (from, into): into[into] += count[from]; from >= src_ncols or into >= out_ncols
+ *       is MCX_ERR_ARG.  A line whose mapped counts are all zero is dropped.  piece_stats (or NULL): the lines of this
+ *       piece.  A malformed line is MCX_ERR_INVAL (mcx_pjoin_error: the refusal of mcx_graph_links_load_text, or
+ *       MCX_LINKS_COUNT_COLUMNS, and the byte offset of the first bad line); nothing of a refused piece is stored, and
+ *       nothing of a piece that met MCX_ERR_NOMEM.  Synchronous.
+ *   mcx_pjoin_finish      the merged body to the sink (or NULL: totals only): per k-mer, in ascending order of the k-mer
+ *       text, `<kmer> <nlinks>` and its links `<F|R> <njuncs> <c0,..,cN-1> <juncs>`, F before R, junction strings in text
+ *       order, a prefix before its extensions.  stats (or NULL): as mcx_pjoin_get_stats.  The store is kept.
+ *   mcx_pjoin_phases      host-clock milliseconds so far of the six phases (tools/bench_pjoin.py): upload, lines,
+ *       parse + store, sort, reduce, text. */
+typedef struct mcx_pjoin mcx_pjoin;
+typedef struct { uint64_t kmer_lines, link_lines, links_kept, kmers_n_mismatch /* `<kmer> <n>` with n != the link lines that follow */; } mcx_pjoin_piece_stats;
+typedef struct {
+  uint64_t kmer_lines, link_lines, links_kept, kmers_n_mismatch; /* summed over the accepted pieces */
+  uint64_t kmers, links, path_bytes;                             /* of the merged output (mcx_pjoin_finish; path_bytes as mcx_links_info) */
+  uint64_t compactions, store_bytes, peak_store_bytes;           /* the store: times compacted, bytes held now and at most (after an add) */
+} mcx_pjoin_stats;
+int mcx_pjoin_create(mcx_pjoin **h, int kmer_size, int out_ncols, int device);
+int mcx_pjoin_configure(mcx_pjoin *h, const char *key, uint64_t value);
+int mcx_pjoin_buffer(mcx_pjoin *h, size_t bytes, void **ptr);
+int mcx_pjoin_add_text(mcx_pjoin *h, const void *text, uint64_t nbytes, int src_ncols, const int32_t *filter /* nfilter x (from, into) */, int nfilter,
+                       mcx_pjoin_piece_stats *piece_stats /* or NULL */);
+int mcx_pjoin_finish(mcx_pjoin *h, mcx_sink_fn sink, void *ctx, mcx_pjoin_stats *stats /* or NULL */);
+int mcx_pjoin_get_stats(const mcx_pjoin *h, mcx_pjoin_stats *stats);
+int mcx_pjoin_error(const mcx_pjoin *h, int *code, uint64_t *byte_offset);
+int mcx_pjoin_phases(const mcx_pjoin *h, double *ms /* [6] */);
+void mcx_pjoin_destroy(mcx_pjoin *h);
 
 /* Sharded build, exchange format v3 ("reads travel, not occurrences"; odd k in 29..63,
  * mcx_superk_supported(); records are mcx_superk_record_bytes(k) = 16 bytes for one-word keys, 32

@@ -5,7 +5,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmcxgpu.so")
-SOURCES = ["mcx_api.hip", "mcx_kernels.h", "mcx_kmer.h", "mcx_defer.h", "mcx_superk.h", "mcx_streamfc.h", "mcx_multi.h", "mcx_ubench.h", "mcx_infer.h", "mcx_clean.h", "mcx_unitigs.h", "mcx_pop.h", "mcx_subgraph.h", "mcx_reads.h", "mcx_coverage.h", "mcx_correct.h", "mcx_join.h", "mcx_chunk.h", "mcx_thread.h", "mcx_links.h", "mcx_contigs.h", "mcx_bubbles.h", "mcx_breakpoints.h"]
+SOURCES = ["mcx_api.hip", "mcx_kernels.h", "mcx_kmer.h", "mcx_defer.h", "mcx_superk.h", "mcx_streamfc.h", "mcx_multi.h", "mcx_ubench.h", "mcx_infer.h", "mcx_clean.h", "mcx_unitigs.h", "mcx_pop.h", "mcx_subgraph.h", "mcx_reads.h", "mcx_coverage.h", "mcx_correct.h", "mcx_join.h", "mcx_chunk.h", "mcx_thread.h", "mcx_links.h", "mcx_pjoin.h", "mcx_contigs.h", "mcx_bubbles.h", "mcx_breakpoints.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 

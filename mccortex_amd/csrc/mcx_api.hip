@@ -5397,6 +5397,8 @@ extern "C" int mcx_records_sorted(const void *recs, uint64_t nrecs, int kmer_siz
 #include "mcx_join.h"
 // `links`: the same
 #include "mcx_links.h"
+// `pjoin`: the line marking, the number lists and the text delivery of mcx_links.h
+#include "mcx_pjoin.h"
 // `contigs`: the line marking of mcx_links.h, the link store of `thread` above
 #include "mcx_contigs.h"
 // `bubbles`: the decomposition of `clean`, the passes A and B of `unitigs`

@@ -541,23 +541,29 @@ extern "C" int mcx_links_hist(mcx_links *l, uint64_t *out)
   return MCX_OK;
 }
 
-// `total` bytes of finished text on the device to a sink, "out_chunk" bytes at a time through pinned memory
-static int links_deliver(mcx_links *l, const uint8_t *d_text, uint64_t total, mcx_sink_fn sink, void *ctx, const char *what)
+// `total` bytes of finished text on the device to a sink, `out_chunk` bytes at a time through the pinned buffer *h_out
+// (grown to a chunk when it is smaller); `links` and `pjoin` deliver their texts through this
+static int text_deliver(hipStream_t st, uint64_t out_chunk, uint8_t **h_out, size_t *h_out_cap, const uint8_t *d_text, uint64_t total, mcx_sink_fn sink, void *ctx,
+                        const char *who, const char *what)
 {
-  const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(l->out_chunk, 1), std::max<uint64_t>(total, 1));
-  if (chunk > l->h_out_cap) {
-    if (l->h_out) (void)hipHostFree(l->h_out);
-    l->h_out = nullptr; l->h_out_cap = 0;
-    HIP_TRY(hipHostMalloc((void **)&l->h_out, chunk, hipHostMallocDefault));
-    l->h_out_cap = chunk;
+  const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(out_chunk, 1), std::max<uint64_t>(total, 1));
+  if (chunk > *h_out_cap) {
+    if (*h_out) (void)hipHostFree(*h_out);
+    *h_out = nullptr; *h_out_cap = 0;
+    HIP_TRY(hipHostMalloc((void **)h_out, chunk, hipHostMallocDefault));
+    *h_out_cap = chunk;
   }
   for (uint64_t c0 = 0; c0 < total; c0 += chunk) {
     const uint64_t nb = std::min(total, c0 + chunk) - c0;
-    HIP_TRY(hipMemcpyAsync(l->h_out, d_text + c0, nb, hipMemcpyDeviceToHost, l->stream));
-    HIP_TRY(hipStreamSynchronize(l->stream));
-    if (sink(ctx, l->h_out, (size_t)nb) != 0) return fail(MCX_ERR_SINK, "links: the sink refused the %s", what);
+    HIP_TRY(hipMemcpyAsync(*h_out, d_text + c0, nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (sink(ctx, *h_out, (size_t)nb) != 0) return fail(MCX_ERR_SINK, "%s: the sink refused the %s", who, what);
   }
   return MCX_OK;
+}
+static int links_deliver(mcx_links *l, const uint8_t *d_text, uint64_t total, mcx_sink_fn sink, void *ctx, const char *what)
+{
+  return text_deliver(l->stream, l->out_chunk, &l->h_out, &l->h_out_cap, d_text, total, sink, ctx, "links", what);
 }
 
 #define LK_LAUNCH(NAME, ITEMS, ...)                                                                       \

@@ -32,6 +32,8 @@ SYMBOLS = [
     "mcx_join_create", "mcx_join_configure", "mcx_join_get_stats", "mcx_join_phases", "mcx_join_buffer", "mcx_join_add_records", "mcx_join_finish", "mcx_join_destroy",
     "mcx_links_create", "mcx_links_configure", "mcx_links_buffer", "mcx_links_add_text", "mcx_links_get_stats", "mcx_links_hist", "mcx_links_error",
     "mcx_links_phases", "mcx_links_destroy",
+    "mcx_pjoin_create", "mcx_pjoin_configure", "mcx_pjoin_buffer", "mcx_pjoin_add_text", "mcx_pjoin_finish", "mcx_pjoin_get_stats", "mcx_pjoin_error",
+    "mcx_pjoin_phases", "mcx_pjoin_destroy",
 ]
 
 
@@ -241,6 +243,21 @@ class LinksStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class PjoinPieceStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("kmer_lines", "link_lines", "links_kept", "kmers_n_mismatch")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class PjoinStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("kmer_lines", "link_lines", "links_kept", "kmers_n_mismatch", "kmers", "links", "path_bytes",
+                                          "compactions", "store_bytes", "peak_store_bytes")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class UnitigsArrays(C.Structure):
     """mcx_unitigs_arrays (device pointers)"""
     _fields_ = [(n, C.c_void_p) for n in ("keys", "unitig", "rank", "orient", "first", "length")]
@@ -313,6 +330,16 @@ def lib():
     L.mcx_links_phases.argtypes = [vp, C.POINTER(C.c_double)]
     L.mcx_links_destroy.argtypes = [vp]
     L.mcx_links_destroy.restype = None
+    L.mcx_pjoin_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int]
+    L.mcx_pjoin_configure.argtypes = [vp, C.c_char_p, C.c_uint64]
+    L.mcx_pjoin_buffer.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
+    L.mcx_pjoin_add_text.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, C.c_int, C.POINTER(PjoinPieceStats)]
+    L.mcx_pjoin_finish.argtypes = [vp, SINK_FN, vp, C.POINTER(PjoinStats)]
+    L.mcx_pjoin_get_stats.argtypes = [vp, C.POINTER(PjoinStats)]
+    L.mcx_pjoin_error.argtypes = [vp, C.POINTER(C.c_int), u64p]
+    L.mcx_pjoin_phases.argtypes = [vp, C.POINTER(C.c_double)]
+    L.mcx_pjoin_destroy.argtypes = [vp]
+    L.mcx_pjoin_destroy.restype = None
     L.mcx_graph_unitig_stats.argtypes = [vp, vp]
     L.mcx_graph_clean.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(CleanStats), vp]
     L.mcx_graph_pop_bubbles.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PopStats)]
@@ -1086,7 +1113,7 @@ class Join:
 LINKS_CLEAN, LINKS_HIST = 1, 2
 LINKS_REFUSALS = {1: "bad_kmer_line", 2: "bad_orient", 3: "bad_number", 4: "multi_colour", 5: "bad_junction", 6: "njuncs_range",
                   7: "njuncs_length", 8: "no_seq", 9: "no_juncpos", 10: "juncpos_count", 11: "seq_length", 12: "seq_base",
-                  13: "link_before_kmer"}
+                  13: "link_before_kmer", 14: "count_columns"}
 
 
 class Links:
@@ -1158,6 +1185,68 @@ class Links:
         ms = (C.c_double * 8)()
         _check(self.L.mcx_links_phases(self.h, ms))
         return dict(zip(("upload_ms", "lines_ms", "parse_ms", "sort_ms", "reduce_lcp_ms", "tree_ms", "written_ms", "text_ms"), [float(x) for x in ms]))
+
+
+class Pjoin:
+    """`pjoin` on the device: the bodies of version-4 .ctp files merged by a sort and a segmented reduce of per-colour
+    counts (no graph, no table)."""
+
+    def __init__(self, kmer_size, out_ncols, device=0):
+        self.L = lib()
+        self.h = None
+        self.k, self.ncols = kmer_size, out_ncols
+        h = C.c_void_p()
+        _check(self.L.mcx_pjoin_create(C.byref(h), kmer_size, out_ncols, device))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.L.mcx_pjoin_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def configure(self, key, value):
+        _check(self.L.mcx_pjoin_configure(self.h, key.encode(), int(value)))
+
+    def add(self, text, src_ncols=1, filter=None):
+        """text: lines of the body of a file with src_ncols colours; filter: [(from, into)], None = colour c into
+        colour c; -> the piece's line counts as a dict"""
+        text = bytes(text)
+        pairs = [(c, c) for c in range(src_ncols)] if filter is None else list(filter)
+        flt = np.array(pairs, dtype=np.int32).reshape(-1, 2)
+        ps = PjoinPieceStats()
+        _check(self.L.mcx_pjoin_add_text(self.h, text, len(text), src_ncols, _ptr(flt) if len(flt) else None, len(flt), C.byref(ps)))
+        return ps.as_dict()
+
+    def finish(self, keep=True):
+        """-> the merged body as bytes (k-mers in ascending text order); keep=False drops the bytes (benchmarks)"""
+        parts = []
+
+        def sink(_ctx, ptr, n):
+            parts.append(C.string_at(ptr, n) if keep else n)
+            return 0
+
+        st = PjoinStats()
+        _check(self.L.mcx_pjoin_finish(self.h, SINK_FN(sink), None, C.byref(st)))
+        self.chunks = [len(p) if keep else p for p in parts]
+        return b"".join(parts) if keep else b""
+
+    def stats(self):
+        st = PjoinStats()
+        _check(self.L.mcx_pjoin_get_stats(self.h, C.byref(st)))
+        return st.as_dict()
+
+    def error(self):
+        """after an McxError of code MCX_ERR_INVAL: (refusal name, byte offset of the first bad line in the text)"""
+        code, off = C.c_int(0), C.c_uint64(0)
+        _check(self.L.mcx_pjoin_error(self.h, C.byref(code), C.byref(off)))
+        return LINKS_REFUSALS.get(code.value, code.value), int(off.value)
+
+    def phases(self):
+        ms = (C.c_double * 6)()
+        _check(self.L.mcx_pjoin_phases(self.h, ms))
+        return dict(zip(("upload_ms", "lines_ms", "parse_store_ms", "sort_ms", "reduce_ms", "text_ms"), [float(x) for x in ms]))
 
 
 def records_sorted(recs, kmer_size, ncols, device=0):

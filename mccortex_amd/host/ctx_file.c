@@ -254,6 +254,25 @@ static void reader_set_filter(ctx_reader *r, size_t into_offset)
   free(from); free(into);
 }
 
+char *ctx_arg_path(const char *input)
+{
+  const graph_arg ga = graph_arg_split(input);
+  char *path = calloc(ga.path.n + 1, 1);
+  if (!path) die("Out of memory");
+  memcpy(path, ga.path.s, ga.path.n);
+  return path;
+}
+
+void ctx_arg_filter(const char *input, uint32_t num_cols, size_t into_offset, col_filter **filter, size_t *nfilter, size_t *into_ncols)
+{
+  ctx_reader r;
+  memset(&r, 0, sizeof(r));
+  r.input = (char *)input;
+  r.num_cols = num_cols;
+  reader_set_filter(&r, into_offset);
+  *filter = r.filter; *nfilter = r.nfilter; *into_ncols = r.into_ncols;
+}
+
 /* ---- header reader, driven by a description of docs/file_formats/graph_file_format.txt
  * (checks and messages of graph_file_read_header: graph_file_reader.c:78-260) ---- */
 typedef enum { FT_U8, FT_U32, FT_U64, FT_LDBL, FT_TEXT } field_type;

@@ -138,6 +138,11 @@ bool ctx_reader_from_direct(const ctx_reader *r); /* file_filter_from_direct: no
 /* graph_write_header (graph_writer.c:62-110): the parsed header as it is, no merging */
 size_t ctx_write_header_raw(FILE *fh, const ctx_reader *r);
 void ctx_reader_close(ctx_reader *r);
+/* the same argument syntax for a file that is no .ctx (`pjoin`'s .ctp inputs): the path between the colour lists (to be
+ * freed), and, once the file's colour count is known, the filter as ctx_reader_open sets it (*filter to be freed);
+ * dies with "Invalid filter path" as ctx_reader_open does */
+char *ctx_arg_path(const char *input);
+void ctx_arg_filter(const char *input, uint32_t num_cols, size_t into_offset, col_filter **filter, size_t *nfilter, size_t *into_ncols);
 
 /* cleaning_pick_kmer_threshold (src/tools/clean_graph.c): the unitig cleaning threshold from the k-mer coverage
  * histogram (arrlen bins), or -1; the outputs may be NULL (clean_thresh.c) */
@@ -202,6 +207,16 @@ bool ctp_hdr_first_command_key(const char *hdr, size_t n, char *key, size_t keyl
 char *ctp_hdr_edit(const char *hdr, size_t n, const char *file_key, const char *command, uint64_t nkmers, uint64_t npaths, uint64_t nbytes,
                    size_t *out_len, const char **why);
 size_t ctp_cut(const char *buf, size_t n);
+/* ---- the header `pjoin` writes, merged from its inputs' headers as text (ctp_merge.c) ---- */
+bool ctp_hdr_sample(const char *hdr, size_t n, size_t colour, const char **b, const char **e); /* the JSON string as it stands */
+typedef struct { uint64_t *len, *cnt; size_t n, cap; } ctp_hist; /* ascending lengths, {NULL, NULL, 0, 0} to begin with */
+void ctp_hist_add(ctp_hist *h, uint64_t len, uint64_t count);
+void ctp_hist_free(ctp_hist *h);
+bool ctp_hdr_hist_add(const char *hdr, size_t n, size_t colour, ctp_hist *h);
+bool ctp_hdr_command_at(const char *hdr, size_t n, size_t i, const char **b, const char **e, const char **kb, const char **ke);
+typedef struct { const char *hdr; size_t len; const col_filter *filter; size_t nfilter; const char *path; } ctp_merge_input;
+const char *ctp_merge_header(ctp_str *out, const ctp_merge_input *in, size_t nin, size_t kmer_size, size_t out_ncols, const char *file_key, const char *command,
+                             uint64_t nkmers, uint64_t npaths, uint64_t nbytes, char *err, size_t errlen);
 typedef int (*ctp_read_fn)(void *ctx, void *dst, unsigned n); /* as gzread: bytes read, 0 at the end, < 0 on failure */
 typedef char *(*ctp_grow_fn)(void *ctx, size_t bytes);        /* a new buffer of `bytes`; the old one is gone */
 typedef struct {
@@ -231,6 +246,7 @@ int ctx_correct(int argc, char **argv);     /* src/commands/ctx_correct.c */
 int ctx_thread(int argc, char **argv);      /* src/commands/ctx_thread.c */
 int ctx_join(int argc, char **argv);        /* src/commands/ctx_join.c */
 int ctx_links(int argc, char **argv);       /* src/commands/ctx_links.c */
+int ctx_pjoin(int argc, char **argv);       /* src/commands/ctx_pjoin.c */
 int ctx_contigs(int argc, char **argv);     /* src/commands/ctx_contigs.c */
 int ctx_bubbles(int argc, char **argv);     /* src/commands/ctx_bubbles.c */
 int ctx_breakpoints(int argc, char **argv); /* src/commands/ctx_breakpoints.c */

@@ -69,6 +69,7 @@ int main(int argc, char **argv)
   else if (!strcmp(argv[1], "correct")) func = ctx_correct; /* (as `coverage`: not in the pinned texts) */
   else if (!strcmp(argv[1], "thread")) func = ctx_thread; /* (as `coverage`: not in the pinned texts) */
   else if (!strcmp(argv[1], "links")) func = ctx_links; /* (as `coverage`: not in the pinned texts) */
+  else if (!strcmp(argv[1], "pjoin")) func = ctx_pjoin; /* (as `coverage`: not in the pinned texts) */
   else if (!strcmp(argv[1], "contigs")) func = ctx_contigs; /* (as `coverage`: not in the pinned texts) */
   else if (!strcmp(argv[1], "bubbles")) func = ctx_bubbles; /* (as `coverage`: not in the pinned texts) */
   else if (!strcmp(argv[1], "breakpoints")) func = ctx_breakpoints; /* (the same) */
