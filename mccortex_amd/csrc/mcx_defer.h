@@ -108,7 +108,11 @@ template <int W> __device__ __forceinline__ Kmer<W> tuple_q(const Kmer<W> &t)
 
 // The sorted tile is staged and written out in kRounds rounds of kStage tuples: the staging
 // area is what limits blocks per CU (W=2: 84 KB for a whole tile = 1 block, 46 KB = 3 blocks).
-constexpr int kRounds = 2;  // (1 round: k_stream_bin 22.8 -> 31.2 ms at C2, round 3)
+// (1 round: k_stream_bin 22.8 -> 31.2 ms at C2, round 3 -- a whole-tile staging area halved the
+// blocks per CU then.  The 512-thread one-word k_stream_bin no longer takes these two fixed rounds:
+// it is register-limited to 2 blocks per CU, which leaves each block 80 KB of the 160 KB LDS, enough
+// to stage every tile of 151-byte records in ONE round -- StreamLdsWide below.)
+constexpr int kRounds = 2;
 constexpr int kStage = kTile / kRounds;
 
 // Geometry of a binning block: T threads, TILE tuples per tile (staged in kRounds rounds).  The
@@ -116,8 +120,15 @@ constexpr int kStage = kTile / kRounds;
 // sub-table bin are twice as long (128 B), so fewer of its lines are written in two halves.
 template <int T_, int TILE_, int R_ = kRounds> struct Geo {
   static constexpr int kT = T_, kTileG = TILE_, kRoundsG = R_, kStageG = TILE_ / R_;
+  static constexpr bool kDynG = false;  // every tile takes all kRoundsG rounds
 };
 using Geo256 = Geo<kThreads, kTile>;
+// Geometry whose staging area is sized apart from the tile: a tile of n tuples takes ceil(n / STAGE) rounds (at
+// least one), a number the kernel works out per tile (block-uniform); kRoundsG is the most a tile can take.
+template <int T_, int TILE_, int STAGE_> struct GeoDyn {
+  static constexpr int kT = T_, kTileG = TILE_, kStageG = STAGE_, kRoundsG = (TILE_ + STAGE_ - 1) / STAGE_;
+  static constexpr bool kDynG = true;
+};
 
 // LDS working set of one binning block (NB = histogram capacity)
 template <int W, int NB, bool FULL, class G = Geo256> struct BinLds {
@@ -133,6 +144,24 @@ template <int W, int NB, bool FULL, class G = Geo256> struct BinLds {
   uint32_t wsum[G::kT / 64];
   uint16_t sbin[G::kStageG];
   uint8_t se[FULL ? G::kStageG : 16];
+};
+
+// LDS working set of the 512-thread k_stream_bin (packed region bins, two 4096-position tiles sorted as one tile
+// of 8192).  The kernel is register-limited to 2 blocks per CU, so a block may use half of the 160 KB LDS.
+// 8192 positions of 151-byte records (150 bases and a newline, k = 31) hold at most 54 * 120 + 38 = 6518 k-mer
+// starts: a staging area of 13 * 512 = 6656 tuples takes such a tile in ONE round, and only a tile of longer reads
+// (up to 8192 tuples) takes a second.  No rnk[]: the arrival index of a tuple is the return value of the counting
+// atomic, bin_rank() is k_tuples_bin's alone.  NB = 512: 75,312 bytes + 3,520 static = 78,832 per block.
+constexpr int kStageWide = 13 * 512;
+template <int W, int NB> struct StreamLdsWide {
+  using geo = GeoDyn<2 * kThreads, 2 * kTile, kStageWide>;
+  uint64_t skey[geo::kStageG * W];
+  unsigned long long gbase[NB];  // as in BinLds
+  uint32_t cnt[NB + 64];
+  uint32_t off[NB + 64];
+  uint32_t wsum[geo::kT / 64];
+  uint16_t sbin[geo::kStageG];
+  uint8_t se[16];
 };
 
 // The thread index, opaque to the optimiser: what is derived from it inside a tile loop (LDS
@@ -339,7 +368,20 @@ __device__ __forceinline__ void bin_writeout(LDS &L, int round, const BinSpec &b
     const uint32_t b = L.sbin[q];
     emit(p, b, L.gbase[b], L.skey[q * W], W == 2 ? L.skey[q * W + W - 1] : 0);
   }
-  if (round + 1 < LDS::geo::kRoundsG) __syncthreads();  // staging is reused by the next round
+  // staging is reused by the next round (a kDynG kernel takes a barrier of its own only before a round that exists)
+  if (!LDS::geo::kDynG && round + 1 < LDS::geo::kRoundsG) __syncthreads();
+}
+
+// Placement for a kDynG geometry: the round stages sorted positions [lo, lo + span).  (Trash positions lie at or
+// beyond the tile's size and so outside every round: span never reaches past the tile.)
+template <int W, class LDS>
+__device__ __forceinline__ void bin_place_at(LDS &L, uint32_t lo, uint32_t span, uint32_t p, uint32_t local, const Kmer<W> &t)
+{
+  const uint32_t q = p - lo;
+  if (q >= span) return;
+  L.skey[q * W] = t.w[0];
+  if (W == 2) L.skey[q * W + 1] = t.w[W - 1];
+  L.sbin[q] = (uint16_t)local;
 }
 
 // The lane's 16 k-mers and their reverse complements as windows of two 96-bit registers (one-word
@@ -427,7 +469,10 @@ __global__ __launch_bounds__(T, (W == 1 ? 4 : 3)) void k_stream_bin(StreamArgs a
   const uint64_t a_tile0 = a_arg.tile0, a_ntiles = a_arg.ntiles;
   const uint32_t t_lb1 = isink_arg.t.lb1, t_lbq = isink_arg.t.lb1 + isink_arg.t.lbo, t_part = isink_arg.t.part;
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
-  using LDS = BinLds<W, NB, FULL, Geo<T, T * kPosPerLane>>;
+  using LDS = std::conditional_t<T == 2 * kThreads, StreamLdsWide<W, NB>, BinLds<W, NB, FULL, Geo<T, T * kPosPerLane>>>;
+  static_assert(!LDS::geo::kDynG || W != 1 || NB != 512 ||
+                2 * (sizeof(LDS) + sizeof(s_code_h) + sizeof(s_inv_h) + sizeof(Cold)) <= 160 * 1024,
+                "two blocks of the wide stream kernel fit the CU's 160 KiB of LDS");
   LDS &L = *reinterpret_cast<LDS *>(dyn_lds);
 
   const int tid0 = threadIdx.x & (kThreads - 1);
@@ -461,7 +506,10 @@ __global__ __launch_bounds__(T, (W == 1 ? 4 : 3)) void k_stream_bin(StreamArgs a
     // what a slower wave may still be reading, the staging area and the bin bases, is next
     // written after the three barriers of bin_reserve.)
     tile_stage<PK>(a_arg, pre, tid, s_code, s_inv);
-    for (uint32_t b = tid_blk; b < bs.nlocal + 64; b += T) { L.cnt[b] = 0; L.rnk[b] = 0; }
+    for (uint32_t b = tid_blk; b < bs.nlocal + 64; b += T) {
+      L.cnt[b] = 0;
+      if constexpr (!LDS::geo::kDynG) L.rnk[b] = 0;  // (StreamLdsWide has none: nothing here ranks with it)
+    }
     if (tid < 4) { s_code[kChunks + tid] = 0; s_inv[kChunks / 2 + tid] = 0xFFFFFFFFu; }
     {
       const uint64_t tn = tile + (uint64_t)gridDim.x * H;
@@ -634,14 +682,38 @@ __global__ __launch_bounds__(T, (W == 1 ? 4 : 3)) void k_stream_bin(StreamArgs a
       // it spilled sixteen of them)
       if ((j & 3) == 3) asm volatile("" : "+v"(tle[j - 3]), "+v"(tle[j - 2]), "+v"(tle[j - 1]), "+v"(tle[j]));
     }
-    bin_commit<LDS, NB>(L, bs, out, ob0, res);
-    MCX_PH(3)
-    for (int round = 0; round < kRounds; round++) {
+    if constexpr (LDS::geo::kDynG) {
+      // ceil(n / stage) rounds, block-uniform: one for a tile of 151-byte records, two for a tile of long reads.
+      // Round 0 always runs, also with n = 0: its write-out's entry barrier is the one the top of the next tile
+      // relies on.  The reservations' round trip overlaps round 0's placement, which needs only off[]:
+      // bin_commit, the first reader of res.g0, comes after it (phase 3 is then the off[] reads alone and the
+      // commit counts to phase 4).
+      constexpr uint32_t kSt = LDS::geo::kStageG, kTl = LDS::geo::kTileG;
+      static_assert(LDS::geo::kRoundsG == 2 && !FULL, "at most one round after the first");
+      const uint32_t n = __builtin_amdgcn_readfirstlane(L.off[bs.nlocal]);
+      MCX_PH(3)
 #pragma unroll
-      for (int j = 0; j < kPosPerLane; j++)
-        bin_place<W, FULL, LDS>(L, round, FULL ? (tle[j] >> 12) & 0xfffu : tle[j] >> 12, tle[j] & 0xfffu, tk[j], tle[j] >> 24);
-      bin_writeout<W, ONECOL, FULL, SH, LDS>(L, round, bs, out, ob0, 0, isink, n_novel, full);
-      if (round == 0) { MCX_PH(4) } else { MCX_PH(5) }
+      for (int j = 0; j < kPosPerLane; j++) bin_place_at<W, LDS>(L, 0, kSt, tle[j] >> 12, tle[j] & 0xfffu, tk[j]);
+      bin_commit<LDS, NB>(L, bs, out, ob0, res);
+      bin_writeout<W, ONECOL, FULL, SH, LDS>(L, 0, bs, out, ob0, 0, isink, n_novel, full);
+      MCX_PH(4)
+      if (n > kSt) {
+        __syncthreads();  // staging is reused
+#pragma unroll
+        for (int j = 0; j < kPosPerLane; j++) bin_place_at<W, LDS>(L, kSt, kTl - kSt, tle[j] >> 12, tle[j] & 0xfffu, tk[j]);
+        bin_writeout<W, ONECOL, FULL, SH, LDS>(L, 1, bs, out, ob0, 0, isink, n_novel, full);
+        MCX_PH(5)
+      }
+    } else {
+      bin_commit<LDS, NB>(L, bs, out, ob0, res);
+      MCX_PH(3)
+      for (int round = 0; round < kRounds; round++) {
+#pragma unroll
+        for (int j = 0; j < kPosPerLane; j++)
+          bin_place<W, FULL, LDS>(L, round, FULL ? (tle[j] >> 12) & 0xfffu : tle[j] >> 12, tle[j] & 0xfffu, tk[j], tle[j] >> 24);
+        bin_writeout<W, ONECOL, FULL, SH, LDS>(L, round, bs, out, ob0, 0, isink, n_novel, full);
+        if (round == 0) { MCX_PH(4) } else { MCX_PH(5) }
+      }
     }
   }
   MCX_PH_DUMP(0)

@@ -13,7 +13,7 @@ import mccortex_amd as mcx
 
 NAMES = {
     0: ("k_stream_bin", ["stage tile + zero counters + barrier", "masks + 16 positions (k-mer, canonical, hash, histogram atomic)",
-                         "bin_reserve (scan, 3 barriers, reservations issued)", "arrival -> sorted position, bin_commit",
+                         "bin_reserve (scan, 3 barriers, reservations issued)", "arrival -> sorted position, bin_commit (512 threads: the commit counts to round 0)",
                          "round 0: place + barrier + write-out", "round 1: place + barrier + write-out", "loop top", "tiles"]),
     1: ("k_tuples_bin", ["zero counters + 2 barriers", "tuple loads + sub_hash + histogram atomic", "bin_reserve", "rank atomics + bin_commit",
                          "round 0: place + write-out", "round 1: place + write-out", "chunk index arithmetic / skipped chunks", "tiles"]),
