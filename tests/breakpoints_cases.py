@@ -2,6 +2,9 @@
 reach every rule named there), test_gpu_breakpoints.py (which runs them on the device) and test_breakpoints_cli.py.  Small
 graphs at k = 11, 31 and 33 (keys of one and two words): a reference of one to three chromosomes and one or two sample
 colours; the reference colour is the last one and is empty before the call.  min_ref is 5 unless a case says otherwise.
+tests/golden/breakpoints.json pins these by name.  wide_cases() is the same structures at k = 63, 65, 95, 97 and 127 (keys
+of two, three and four words, the top word full or holding two bits; up to 675 k-mers), which no golden pins: there the
+device is compared with the restatement alone.
 
 Structures (upper-case names are random stretches without a repeated k-mer, a b c d are single bases that differ; M is
 min_ref):
@@ -47,6 +50,7 @@ import breakpoints_restate as B  # noqa: E402
 from bubbles_cases import pieces, bases  # noqa: E402
 
 KS = (11, 31, 33)
+WIDE_KS = (63, 65, 95, 97, 127)  # a full and a 2-bit top word at keys of two, three and four words
 M = 5
 
 
@@ -237,10 +241,10 @@ def run(case, **kw):
 
 
 @functools.lru_cache(maxsize=None)
-def cases():
+def cases(ks=KS):
     out = []
     made = {}
-    for k in KS:
+    for k in ks:
         for name, make, (mn, mx, edges), need in SPECS:
             for salt in range(200):
                 key = (make.__name__, k, salt)
@@ -258,3 +262,8 @@ def cases():
             else:
                 raise AssertionError("no graph for %s at k=%d" % (name, k))
     return tuple(out)
+
+
+def wide_cases():
+    """the same structures at WIDE_KS; no golden pins these, the restatement is the oracle"""
+    return cases(WIDE_KS)

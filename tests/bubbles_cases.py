@@ -1,7 +1,9 @@
 """The cases of the `bubbles` tests, built on the CPU and shared by test_bubbles_restate.py (which asserts that they reach
 every rule named there), test_gpu_bubbles.py (which runs them on the device) and test_bubbles_cli.py.  Small graphs at
 k = 11, 31 and 33 (keys of one and two words) from a few sequences each, 2 to 4 colours; max_allele and max_flank lie
-between 3 and 100.
+between 3 and 100.  tests/golden/bubbles.json pins these by name.  wide_cases() is the same structures at k = 63, 65, 95, 97
+and 127 (keys of two, three and four words, the top word full or holding two bits) with the limits of 100 grown to 3 k,
+which no golden pins: there the device is compared with the restatement alone.
 
 Structures (upper-case names are random stretches without a repeated k-mer, a b c d are single bases that differ):
   snp      L a R | L b R | L a R, and in colour 0 also Z R[4:]: a SNP between colours called from both sides with branches
@@ -30,6 +32,7 @@ import clean_restate as R  # noqa: E402
 import bubbles_restate as B  # noqa: E402
 
 KS = (11, 31, 33)
+WIDE_KS = (63, 65, 95, 97, 127)  # a full and a 2-bit top word at keys of two, three and four words
 
 
 def pieces(rng, k, lens):
@@ -132,12 +135,19 @@ def run(case):
     return B.call(case["graph"], case["k"], case["ncols"], p["max_allele"], p["max_flank"], p["haploid"], p["keep_serial"])
 
 
+def limit(n, k):
+    """a limit of SPECS at k: those of 100 grow with a wide k (an allele of `serial` alone is some 2 k k-mers long) and
+    are 100 at every k of KS; those of 3, 5 and 7 stay"""
+    return max(100, 3 * k) if n == 100 else n
+
+
 @functools.lru_cache(maxsize=None)
-def cases():
+def cases(ks=KS):
     out = []
     graphs = {}
-    for k in KS:
-        for name, make, (ma, mf, hap, ks), need in SPECS:
+    for k in ks:
+        for name, make, (ma, mf, hap, serial_kept), need in SPECS:
+            ma, mf = limit(ma, k), limit(mf, k)
             for salt in range(200):
                 key = (make.__name__, k, salt)
                 if key not in graphs:
@@ -145,7 +155,7 @@ def cases():
                     graphs[key] = (R.build(seqs, k), len(seqs), seqs)
                 graph, ncols, seqs = graphs[key]
                 case = {"name": "%s_k%d" % (name, k), "k": k, "ncols": ncols, "graph": graph, "seqs": seqs,
-                        "params": {"max_allele": ma, "max_flank": mf, "haploid": tuple(hap), "keep_serial": ks}}
+                        "params": {"max_allele": ma, "max_flank": mf, "haploid": tuple(hap), "keep_serial": serial_kept}}
                 _, _, stats, events = run(case)
                 if all(stats.get(n, 0) or events.get(n, 0) for n in need):
                     out.append(case)
@@ -153,3 +163,8 @@ def cases():
             else:
                 raise AssertionError("no graph for %s at k=%d" % (name, k))
     return tuple(out)
+
+
+def wide_cases():
+    """the same structures at WIDE_KS; no golden pins these, the restatement is the oracle"""
+    return cases(WIDE_KS)

@@ -1,7 +1,9 @@
 """The cases of the `contigs` tests, built on the CPU and shared by test_contigs_restate.py (which asserts that they
 reach every status and every stop cause) and test_gpu_contigs.py (which runs them on the device).  Small graphs at
 k = 5, 9, 31 and 33 from a few sequences each; the links are those `thread` makes of reads (thread_restate.py) or are put
-down by hand where a case needs links that no read makes.
+down by hand where a case needs links that no read makes.  tests/golden/contigs.json pins these by name.  wide_cases() is
+the same structures at k = 63, 65, 95, 97 and 127 (keys of two, three and four words, the top word full or holding two
+bits), which no golden pins: there the device is compared with the restatement alone.
 
 Structures (upper-case names are random stretches without a repeated k-mer):
   repeat   U1 R U2 R U3: R is entered two ways and left two ways.  The reads U1 R U2 and U2 R U3 give the link that
@@ -27,6 +29,7 @@ import contigs_restate as G  # noqa: E402
 import thread_restate as T  # noqa: E402
 
 KS = (5, 9, 31, 33)
+WIDE_KS = (63, 65, 95, 97, 127)  # a full and a 2-bit top word at keys of two, three and four words
 
 
 def other(c, by=1):
@@ -92,9 +95,9 @@ def merge_seqs(k, salt=2):
 
 
 @functools.lru_cache(maxsize=None)
-def cases():
+def cases(ks=KS):
     out = []
-    for k in KS:
+    for k in ks:
         # ---- repeat ----
         u1, rep, u2, u3 = repeat_genome(k)
         genome = u1 + rep + u2 + rep + u3
@@ -182,6 +185,11 @@ def cases():
         seed = T.kmer_str(node_at(sample, 1, k)[0], k)
         out.append(mk("rho", k, graph, [(n[0], n[1], (b, b), 1)], {}, ncols=2, flags=G.NO_MISSING_CHECK, seeds=[seed]))
     return out
+
+
+def wide_cases():
+    """the same structures at WIDE_KS; no golden pins these, the restatement is the oracle"""
+    return cases(WIDE_KS)
 
 
 def run(case):

@@ -26,7 +26,7 @@ import clean_restate as R  # noqa: E402
 import correct_restate as X  # noqa: E402
 import reads_restate as S  # noqa: E402
 
-KS = (11, 31, 33, 63, 95)
+KS = (11, 31, 33, 63, 65, 95, 97, 127)
 # what every configuration reaches at least three times (stats of the restatement, one-way) ...
 COMMON = ("num_perfect", "num_no_kmers", "gaps_filled", "gaps_filled_backward", "gaps_too_short", "gaps_too_long_or_stopped",
           "stops_fork", "stops_repeat", "missing_edges", "end_gaps_extended", "bases_filled")

@@ -1,7 +1,10 @@
 """Inputs for the `links` tests: .ctp bodies made without a graph, from random tries per (k-mer, orientation).
 
 Every distinct junction prefix of a (k-mer, orientation) owns its gap (the bases between the junction before and its
-own) and its filler bases, so links that share a prefix agree on the seq and juncpos of that prefix."""
+own) and its filler bases, so links that share a prefix agree on the seq and juncpos of that prefix.
+
+shared_high_words makes the file whose k-mers agree in their high key words (k = 63, 95, 127), for `links`, for
+Graph.links_load_text / links_text and for the seeds of `contigs`; stored() says what a graph keeps of a body."""
 import random
 
 COMP = {"A": "T", "C": "G", "G": "C", "T": "A"}
@@ -57,27 +60,96 @@ def generated(k, nkmers, seed, max_len=12, noise=True):
             continue
         seen.add(kmer)
         orients = ["R"] if len(blocks) == 1 else rng.choice((["F"], ["R"], ["F", "R"]))
-        lines = []
-        for o in orients:
-            t = Trie(rng, kmer if o == "F" else revcomp(kmer))
-            strs = random_strings(rng, rng.randint(1, 7), max_len)
-            for s in strs:
-                lines.append(t.line(o, s, rng.randint(1, 300)))
-                if rng.random() < 0.25:  # the same link again
-                    lines.append(t.line(o, s, rng.randint(1, 300)))
-                if len(s) > 1 and rng.random() < 0.3:  # one of its prefixes as a link of its own
-                    lines.append(t.line(o, s[:rng.randint(1, len(s) - 1)], rng.randint(1, 300)))
-        rng.shuffle(lines)
-        block = ["%s %d" % (kmer, len(lines))]
-        for ln in lines:
-            if noise and rng.random() < 0.05:
-                block.append(rng.choice(("# a comment", "", "#")))
-            block.append(ln)
-        if noise and rng.random() < 0.1:
-            block.append("")
-        blocks.append("\n".join(block) + "\n")
+        blocks.append(block(rng, kmer, orients, max_len, noise))
     head = "# the body begins\n\n" if noise else ""
     return (head + "".join(blocks)).encode()
+
+
+def block(rng, kmer, orients, max_len=12, noise=True):
+    """the block of one k-mer line as written: up to 7 random links per orientation, some twice, some with a prefix"""
+    lines = []
+    for o in orients:
+        t = Trie(rng, kmer if o == "F" else revcomp(kmer))
+        strs = random_strings(rng, rng.randint(1, 7), max_len)
+        for s in strs:
+            lines.append(t.line(o, s, rng.randint(1, 300)))
+            if rng.random() < 0.25:  # the same link again
+                lines.append(t.line(o, s, rng.randint(1, 300)))
+            if len(s) > 1 and rng.random() < 0.3:  # one of its prefixes as a link of its own
+                lines.append(t.line(o, s[:rng.randint(1, len(s) - 1)], rng.randint(1, 300)))
+    rng.shuffle(lines)
+    out = ["%s %d" % (kmer, len(lines))]
+    for ln in lines:
+        if noise and rng.random() < 0.05:
+            out.append(rng.choice(("# a comment", "", "#")))
+        out.append(ln)
+    if noise and rng.random() < 0.1:
+        out.append("")
+    return "\n".join(out) + "\n"
+
+
+SHARED_KS = (63, 95, 127)  # keys of two, three and four words, the top word full
+
+
+def key_words(kmer):
+    """the key words of a k-mer string, the highest first: the last holds the last 32 bases, the first the rest of k"""
+    k = len(kmer)
+    W = (2 * k + 63) // 64
+    x = 0
+    for c in kmer:
+        x = x << 2 | "ACGT".index(c)
+    return [(x >> (64 * (W - 1 - i))) & (2**64 - 1) for i in range(W)]
+
+
+def shared_high_words(k, seed=None):
+    """-> (body bytes, groups) for a k of SHARED_KS: link blocks whose k-mers come in groups that agree in their high key
+    words, which random k-mers never do.  groups: [(j, k-mers, turned)], the canonical k-mers of a group agree in the key
+    words before word j and differ in word j; where the words below j lie in a group, they sort the other way round than
+    word j.  Every k-mer begins with A and does not end with T, so it is its own canonical form.
+      j = W - 1   three groups of six k-mers that differ in their last two bases only, and a fourth (`turned`) of which
+                  the file holds the reverse complements: the reader has to turn these k-mers and their links round;
+      j < W - 1   from three words on, a group of four per word j >= 1 that share the words above it and 3 to 28 bases
+                  of it, then hold A C G T, and begin word j + 1 with T G C A.
+    The blocks are those of `generated` (links twice, prefixes, comment and empty lines), in shuffled order."""
+    rng = random.Random(k if seed is None else seed)
+    rs = lambda n: "".join(rng.choice("ACGT") for _ in range(n))  # noqa: E731
+    W = (2 * k + 63) // 64
+    first = k - 32 * (W - 1)  # the bases of word 0
+    groups = []
+    for g in range(4):
+        stem = "A" + rs(k - 3)
+        ends = rng.sample([a + b for a in "ACGT" for b in "ACG"], 6)
+        groups.append((W - 1, [stem + e for e in ends], g == 3))
+    for j in range(1, W - 1):
+        at = first + 32 * (j - 1) + rng.randint(3, 28)  # inside word j
+        stem, nxt = "A" + rs(at - 1), first + 32 * j
+        kmers = []
+        for i in range(4):
+            s = stem + "ACGT"[i] + rs(k - at - 1)
+            kmers.append(s[:nxt] + "TGCA"[i] + s[nxt + 1:k - 1] + rng.choice("ACG"))
+        groups.append((j, kmers, False))
+    written = [(revcomp(s) if turned else s) for _, kmers, turned in groups for s in kmers]
+    assert len(set(written)) == len(written)
+    rng.shuffle(written)
+    body = "".join(block(rng, s, ["R"] if i == 1 else rng.choice((["F"], ["R"], ["F", "R"]))) for i, s in enumerate(written))
+    return ("# the body begins\n\n" + body).encode(), groups
+
+
+def stored(body, k):
+    """what a graph keeps of a .ctp body (Graph.links_load_text): [(key, orient, junction bases, nseen)] with every k-mer
+    turned to its canonical form (its links change orientation with it), equal links added up, 255 at the most"""
+    import clean_restate as R
+    per, key, turn = {}, None, 0
+    for ln in body.decode().split("\n"):
+        if ln[:1] in ("A", "C", "G", "T"):
+            x = R.kmer_int(ln.split(" ")[0])
+            key = R.canon(x, k)
+            turn = 0 if key == x else 1
+        elif ln[:2] in ("F ", "R "):
+            cols = ln.split(" ")
+            link = (key, (0 if cols[0] == "F" else 1) ^ turn, tuple("ACGT".index(c) for c in cols[3]))
+            per[link] = min(255, per.get(link, 0) + min(255, int(cols[2])))
+    return [(key, o, b, n) for (key, o, b), n in per.items()]
 
 
 def blocks_of(text):

@@ -174,6 +174,27 @@ def test_breakpoint1_fixture_through_the_command(built, tmp_path):
 
 
 @pytest.mark.gpu
+def test_breakpoints_at_k97(mcx, tmp_path):
+    """one run at keys of four words with two bits in the top one: three chromosomes, the sample built by mccortex127"""
+    maxk, k, d = 127, 97, str(tmp_path)
+    assert os.path.exists(os.path.join(BIN, "mccortex%d" % maxk))
+    case = next(c for c in BC.wide_cases() if c["name"] == "repeat_k%d" % k)
+    rfa, sfa, ctx, out = (os.path.join(d, n) for n in ("ref.fa", "s.fa", "s.ctx", "o.txt.gz"))
+    with open(rfa, "w") as f:
+        f.write("".join(">%s\n%s\n" % (n, s) for n, s in zip(case["names"], case["ref"])))
+    with open(sfa, "w") as f:
+        f.write("".join(">s%d\n%s\n" % (i, s) for i, s in enumerate(case["seqs"][0])))
+    build_graph(maxk, k, sfa, ctx, "col0")
+    rc, so, err = run(maxk, "breakpoints", "-o", out, "--seq", rfa, ctx)
+    assert rc == 0 and so == b"", err[-800:]
+    recs, text, stats, _, with_ref = BC.run(case)
+    hdr, body = split_file(gzip.open(out).read())
+    assert body == text and stats["calls"] > 0 and "  %d calls printed to" % stats["calls"] in err
+    check_header(hdr, maxk, k, 2, len(with_ref), ["col0"], (5, 1000, True), [os.path.realpath(rfa)],
+                 [{"id": n, "length": len(s)} for n, s in zip(case["names"], case["ref"])])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("maxk,k", [(31, 31), (63, 33)])
 def test_two_seq_files_names_cleaned_and_colour_offsets(built, tmp_path, maxk, k):
     d = str(tmp_path)

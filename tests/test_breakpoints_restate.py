@@ -101,6 +101,56 @@ def test_case_set_reaches_every_rule():
         assert ev("repeat")["sort_tie_on_chrom"] and ev("repeat")["one_of_two_runs_ends"]
 
 
+def test_wide_case_set_reaches_every_rule():
+    """the cases at k = 63 .. 127 (keys of two, three and four words), which no golden pins: the conditions that the test
+    above asserts per k of KS, per k of WIDE_KS, and its sums over the wide set alone.  The graphs grow with k (675
+    k-mers at k = 127), so their bound is 800; every call is checked against the reference as for the narrow set"""
+    events, stats, per = collections.Counter(), collections.Counter(), {}
+    needs = dict((s[0], s[3]) for s in BC.SPECS)
+    assert [c["name"] for c in BC.wide_cases()] == ["%s_k%d" % (s[0], k) for k in BC.WIDE_KS for s in BC.SPECS]
+    for c in BC.wide_cases():
+        assert len(c["graph"]) <= 800 and 2 <= c["ncols"] <= 3
+        res = BC.run(c)
+        per[c["name"]] = res
+        events.update(res[3])
+        stats.update(res[2])
+        assert all(res[2].get(n, 0) or res[3].get(n, 0) for n in needs[c["name"].rsplit("_k", 1)[0]]), c["name"]
+        assert res[2]["stop_bound"] == 0 and res[2]["reruns"] == 0
+        if res[1]:
+            self_check(res[1], c["ref"], c["names"], c["k"])
+    assert all(events[e] for e in EVENTS), events
+    assert all(stats[s] for s in STATS), stats
+    for k in BC.WIDE_KS:
+        st = lambda name: per["%s_k%d" % (name, k)][2]  # noqa: E731
+        ev = lambda name: per["%s_k%d" % (name, k)][3]  # noqa: E731
+        for name in BC.NO_CALL:
+            assert per["%s_k%d" % (name, k)][1] == "" and st(name)["calls"] == 0, name
+        for name in BC.NO_BREAK:
+            assert st(name)["breaks"] == 0 and st(name)["ref_added"] == 0
+        for name in ("snp", "insertion", "deletion", "microhom", "junction", "ends"):
+            assert st(name)["calls"] == 2 and st(name)["breaks"] == 2, name  # seen from either side
+        assert ev("snp")["flank3pidx_from_k1"] == 2 and all(r["path_kmers"] == 1 for r in per["snp_k%d" % k][0])
+        assert all(r["path_kmers"] == 0 for r in per["deletion_k%d" % k][0]) and ev("deletion")["flank3pidx_from_k1"] == 2
+        assert ev("microhom")["flank3pidx_below_k1"] == 2 and all(r["path_kmers"] == 0 for r in per["microhom_k%d" % k][0])
+        assert st("snp_maxref")["stop_maxref"] == 4
+        assert st("twosnps")["stop_runs"] and st("twosnps")["calls"] == 4
+        assert ev("inversion")["allele_run_minus"] and st("inversion")["calls"] == 4
+        assert st("lost")["stop_flank"] and st("lost")["flanks_norun"] and st("lost")["allele_walks"] < st("lost")["flank_walks"]
+        assert st("tail")["alleles_norun"] == 1 and st("loop")["stop_repeat"] == 1
+        assert ev("twosucc")["two_nonref_successors"] == 2 and st("twosucc")["calls"] == 4
+        assert [r["num_cols"] for r in per["merged_k%d" % k][0]] == [2, 2] and "cols=0,1\n" in per["merged_k%d" % k][1]
+        assert ev("twopaths")["two_calls_one_break"] == 1
+        assert ev("lacks")["colour_lacks_successor"] and "cols=0\n" in per["lacks_k%d" % k][1] and "cols=1" not in per["lacks_k%d" % k][1]
+        assert st("nocol")["stop_nocolcovg"]
+        assert st("refn")["ref_added"] and st("refn")["calls"] == 2
+        assert ev("exact")["exact_run_kept_5p"] and ev("exact")["exact_run_kept_3p"]
+        assert per["exact_k%d" % k][1] != per["exact_edges_k%d" % k][1]  # the reference's edges change the outcome
+        assert ev("repeat_exact")["exact_run_dropped_5p"] and ev("repeat_exact")["exact_run_dropped_3p"]
+        assert ev("cycleref")["kept_runs_fell"] and st("cycleref")["stop_repeat"] == 1 and ev("cycleref")["exact_run_kept_3p"]
+        assert [r["flank3p_runs"] for r in per["cycleref_k%d" % k][0]] == [1]
+        assert ev("repeat")["sort_tie_on_chrom"] and ev("repeat")["one_of_two_runs_ends"]
+
+
 def test_records_describe_the_text():
     for c in BC.cases():
         recs, text, stats, _, _ = BC.run(c)

@@ -155,6 +155,24 @@ def test_bubbles_of_joined_colour_files(built, tmp_path, maxk, k):
 
 
 @pytest.mark.gpu
+def test_bubbles_at_k97(mcx, tmp_path):
+    """one run at keys of four words with two bits in the top one: colour files built and joined by mccortex127"""
+    maxk, k, d = 127, 97, str(tmp_path)
+    assert os.path.exists(os.path.join(BIN, "mccortex%d" % maxk))
+    case = next(c for c in BC.wide_cases() if c["name"] == "snp_k%d" % k)
+    files = colour_files(case, d, maxk)
+    out = os.path.join(d, "calls.bub.txt.gz")
+    rc, so, err = run(maxk, "bubbles", "-o", out, "-H", "1", "-A", "300", "-F", "5", files[0], *["%d:%s" % (i, p) for i, p in enumerate(files) if i])
+    assert rc == 0 and so == b"", err[-800:]
+    recs, text, stats, _ = B.call(case["graph"], k, case["ncols"], 300, 5, (1,))
+    hdr, body = split_file(gzip.open(out).read())
+    assert body == text and stats["bubbles"] > 0 and counts_in(err, stats)
+    gr = hdr["graph"]
+    assert (gr["num_colours"], gr["kmer_size"], gr["num_kmers_in_graph"]) == (case["ncols"], k, len(case["graph"]))
+    assert hdr["commands"][0]["cmd"][:2] == ["mccortex%d" % maxk, "bubbles"]
+
+
+@pytest.mark.gpu
 def test_keep_serial_haploid_drop_and_defaults(built, tmp_path):
     k = 31
     d = str(tmp_path)

@@ -93,6 +93,41 @@ def test_case_set_reaches_every_rule():
         assert per["cross_k%d" % k][3]["flank_one"]
 
 
+def test_wide_case_set_reaches_every_rule():
+    """the cases at k = 63 .. 127 (keys of two, three and four words), which no golden pins: the conditions that the test
+    above asserts per k of KS, per k of WIDE_KS, and its sums over the wide set alone.  The limits that are 100 there are
+    max(100, 3 k) here; those of 3, 5 and 7 stay"""
+    events, stats, per = collections.Counter(), collections.Counter(), {}
+    assert [c["name"] for c in BC.wide_cases()] == ["%s_k%d" % (s[0], k) for k in BC.WIDE_KS for s in BC.SPECS]
+    for c, spec in zip(BC.wide_cases(), BC.SPECS * len(BC.WIDE_KS)):
+        limits = (3, 5, 7, max(100, 3 * c["k"]))
+        assert c["params"]["max_allele"] in limits and c["params"]["max_flank"] in limits and 2 <= c["ncols"] <= 4
+        assert (c["params"]["max_allele"] < 100) == (spec[2][0] < 100) and (c["params"]["max_flank"] < 100) == (spec[2][1] < 100)
+        recs, text, st, ev = BC.run(c)
+        per[c["name"]] = (recs, text, st, ev)
+        events.update(ev)
+        stats.update(st)
+    assert all(events[e] for e in EVENTS), events
+    assert all(stats[s] for s in STOPS), stats
+    for k in BC.WIDE_KS:
+        recs, text, st, ev = per["snp_k%d" % k]
+        assert st["bubbles"] == 2 and ev["branch_k_kmers"] == 4 and ev["flank_cut"] and ev["3p_first_equal"] and ev["3p_prev_equal"] and ev["dupes_removed"]
+        assert len({r["fork_key"] for r in recs}) == 2  # called from both sides
+        assert per["snp_limit_k%d" % k][2]["stop_limit"] == per["snp_limit_k%d" % k][2]["paths"] and not per["snp_limit_k%d" % k][2]["bubbles"]
+        assert per["indel_k%d" % k][2]["bubbles"] == 2
+        assert per["empty_k%d" % k][3]["branch_empty"] == 2
+        assert all(r["num_branches"] == 3 for r in per["three_k%d" % k][0])
+        assert per["multi_k%d" % k][3]["branch_multi_unitig"]
+        assert per["haploid_k%d" % k][2]["haploid_dropped"] == 2 and per["haploid_k%d" % k][2]["bubbles"] == 0
+        assert per["haploid_off_k%d" % k][2]["haploid_dropped"] == 0 and per["haploid_off_k%d" % k][2]["bubbles"] == 2
+        assert per["haploid_k%d" % k][2]["stop_nolinks"]
+        assert per["serial_k%d" % k][2]["serial_dropped"] == 2 and per["serial_k%d" % k][2]["bubbles"] == 4
+        assert per["serial_kept_k%d" % k][2]["serial_dropped"] == 0 and per["serial_kept_k%d" % k][2]["bubbles"] == 6
+        assert per["nocol_k%d" % k][2]["stop_nocolcovg"] and per["nocol_k%d" % k][3]["popfwd"]
+        assert per["loop_k%d" % k][2]["stop_repeat"] == 1
+        assert per["cross_k%d" % k][3]["flank_one"]
+
+
 def test_a_graph_without_a_fork_gives_nothing():
     graph = R.build([["ACGTTGCATGTCGCATGATGCATGAGAGCT"], ["ACGTTGCATGTCGCATGATGCATGAGAGCT"]], 11)
     recs, text, stats, _ = B.call(graph, 11, 2, 50, 50)

@@ -91,23 +91,34 @@ def test_bench_tool_phases_from_profile_spans():
 
 @pytest.mark.gpu
 def test_build_thread_contigs(built, tmp_path):
+    build_thread_contigs(tmp_path, 31, 31)
+
+
+@pytest.mark.gpu
+def test_build_thread_contigs_k97(mcx, tmp_path):
+    """the same at keys of four words with two bits in the top one"""
+    assert os.path.exists(os.path.join(BIN, "mccortex127"))
+    build_thread_contigs(tmp_path, 127, 97)
+
+
+def build_thread_contigs(tmp_path, maxk, k):
     import random
-    k = 31
     rng = random.Random(99)
     rs = lambda n: "".join(rng.choice("ACGT") for _ in range(n))  # noqa: E731
     rep = rs(k + 12)
     gen = rs(300) + rep + rs(320) + rep + rs(300)
-    reads = [gen[a:a + 250] for a in range(0, len(gen) - 250, 23)] + [gen[-250:]]
+    n = max(250, 4 * k)  # (a read that spans the repeat and a k-mer on either side of it)
+    reads = [gen[a:a + n] for a in range(0, len(gen) - n, 23)] + [gen[-n:]]
     d = str(tmp_path)
     fa = os.path.join(d, "reads.fa")
     with open(fa, "w") as f:
         f.write("".join(">r%d\n%s\n" % (i, s) for i, s in enumerate(reads)))
     ctx, ctp, out, csv = (os.path.join(d, n) for n in ("g.ctx", "l.ctp.gz", "contigs.fa", "conf.csv"))
-    rc, _, err = run(31, "build", "-q", "-k", k, "--sample", "s", "--seq", fa, ctx)
+    rc, _, err = run(maxk, "build", "-q", "-k", k, "--sample", "s", "--seq", fa, ctx)
     assert rc == 0, err[-800:]
-    rc, _, err = run(31, "thread", "-q", "--seq", fa, "-o", ctp, ctx)
+    rc, _, err = run(maxk, "thread", "-q", "--seq", fa, "-o", ctp, ctx)
     assert rc == 0, err[-800:]
-    rc, _, err = run(31, "contigs", "-o", out, "-p", ctp, "-S", csv, ctx)
+    rc, _, err = run(maxk, "contigs", "-o", out, "-p", ctp, "-S", csv, ctx)
     assert rc == 0, err[-800:]
     graph = R.build([reads], k)
     store = T.Store(graph, k).thread(reads)
@@ -123,7 +134,7 @@ def test_build_thread_contigs(built, tmp_path):
     with open(seeds, "w") as f:
         f.write("".join(">s%d\n%s\n" % (i, s) for i, s in enumerate(picks)))
     env = dict(os.environ, MCX_LINKS_PIECE="300")
-    p = subprocess.run([os.path.join(BIN, "mccortex31"), "contigs", "-q", "-f", "-o", out, "-p", ctp, "-s", seeds, "-r", "-N", "2", "-M", ctx],
+    p = subprocess.run([os.path.join(BIN, "mccortex%d" % maxk), "contigs", "-q", "-f", "-o", out, "-p", ctp, "-s", seeds, "-r", "-N", "2", "-M", ctx],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, env=env)
     assert p.returncode == 0, p.stderr.decode()[-800:]
     recs, seq, st = G.assemble(graph, k, links, conf, flags=G.RESEED | G.NO_MISSING_CHECK, ncontigs=2, seeds=picks)

@@ -88,6 +88,53 @@ def test_case_set_reaches_every_status_cause_and_rule():
         assert has(text[0], si) and not has(text[0], sl) and has(text[1], sl)
 
 
+def test_wide_case_set_reaches_what_the_narrow_one_does():
+    """the cases at k = 63 .. 127 (keys of two, three and four words), which no golden pins: the conditions that the test
+    above asserts per k of KS, per k of WIDE_KS, and its sums over the wide set alone"""
+    cases = CC.wide_cases()
+    assert sorted(c["name"] for c in cases) == sorted(c["name"].rsplit("_k", 1)[0] + "_k%d" % k for c in CC.cases() if c["k"] == CC.KS[0] for k in CC.WIDE_KS)
+    steps, stops, events, per, recs_of = collections.Counter(), collections.Counter(), collections.Counter(), {}, {}
+    for c in cases:
+        recs, seq, st = CC.run(c)
+        per[c["name"]], recs_of[c["name"]] = st, (recs, seq)
+        for i in range(9):
+            steps[i] += st["wlk_steps"][i]
+            stops[i] += st["stop_causes"][i]
+        events.update(st["events"])
+    assert all(steps[s] for s in STATUSES), steps
+    assert all(stops[s] for s in range(9)), stops
+    assert stops[G.STOP_UNKNOWN] == sum(st["corrupt_links"] for st in per.values())
+    assert all(events[e] for e in EVENTS), events
+    plain_stats = lambda st: {k2: v for k2, v in st.items() if k2 != "events"}  # noqa: E731
+    for k in CC.WIDE_KS:
+        st = lambda name: per["%s_k%d" % (name, k)]  # noqa: E731
+        assert st("repeat_missing")["stop_causes"][G.STOP_MISSING_PATHS] and not st("repeat_missing")["wlk_steps"][G.USELINKS]
+        assert st("repeat_missing_off")["wlk_steps"][G.USELINKS] and not st("repeat_missing_off")["stop_causes"][G.STOP_MISSING_PATHS]
+        assert st("repeat_split")["stop_causes"][G.STOP_SPLIT_PATHS] == 1
+        assert st("repeat_corrupt")["corrupt_links"] == 1
+        assert st("repeat_low_step")["stop_causes"][G.STOP_LOW_STEP] and st("repeat_low_cumul")["stop_causes"][G.STOP_LOW_CUMUL]
+        assert st("circle")["stop_causes"][G.STOP_CYCLE] == 2
+        rho = st("rho")
+        assert rho["events"]["stopped_by_an_equal_state_after_rounds_with_links"] == 1 and rho["events"]["link_finished_at_fork"] == 1
+        assert any(G.STOP_CYCLE in r["stop_causes"] and r["num_junc"] > 0 and r["wlk_steps"][G.POPFRK_COLFWD] >= 3 for r in recs_of["rho_k%d" % k][0])
+        assert st("colours_c1")["contigs"] > 0
+        assert st("merge_filtered")["events"]["counter_link_filtered"]
+        assert plain_stats(st("merge_filtered")) == plain_stats(st("merge"))
+        chain = st("merge_chain")
+        assert (chain["contigs"], chain["num_reseed_abort"], chain["seeds_not_found"]) == (2, 3, 1)
+        assert st("merge_chain_reseed")["contigs"] == 4
+        assert (st("merge_chain_limit")["contigs"], st("merge_chain_limit")["num_reseed_abort"]) == (1, 0)
+        assert st("repeat_limit")["contigs"] <= 2 and st("repeat_reseed")["contigs"] == 7
+        assert st("colours")["wlk_steps"][G.POPFWD] and st("colours")["stop_causes"][G.STOP_NOCOLCOVG]
+        # with reseeding the contig of i holds l, which the contig of j does not
+        c = next(c for c in cases if c["name"] == "merge_chain_reseed_k%d" % k)
+        recs, seq = recs_of[c["name"]]
+        text = [seq[r["seq_off"]:r["seq_off"] + r["len_nodes"] + k - 1].decode() for r in recs]
+        sj, si, sl = c["params"]["seeds"][:3]
+        has = lambda t, s: s in t or G.kmer_str(G.R.revcomp(G.R.kmer_int(s), k), k) in t  # noqa: E731
+        assert has(text[0], si) and not has(text[0], sl) and has(text[1], sl)
+
+
 def test_confidence_table_shape():
     t = G.conf_table({}, 100)
     assert t == [] and G.conf_csv(t) == "gap_dist\tconfidence_0\n"

@@ -4,7 +4,9 @@ often the "breakpoints_runs" knob was outgrown).  Every case of breakpoints_case
 words); the same, on the handle that holds the reference by then, with "breakpoints_batch" 1 and 2, "grid" 1,
 "breakpoints_chunk" 1, 7 and 64 and "breakpoints_runs" 1; a random 2 kb genome per k whose two sample colours carry
 substitutions, indels, an inversion and a translocation, at two table capacities; second calls with other limits on one
-handle; the breakpoint1 fixture; the ABI symbol and the refusals.  stop_bound is 0 everywhere."""
+handle; the breakpoint1 fixture; the ABI symbol and the refusals.  At k = 63, 65, 95, 97 and 127 (keys of two, three and
+four words): the wide cases without a knob, with "breakpoints_batch" 1 and with "breakpoints_chunk" 7, and the random
+genome.  stop_bound is 0 everywhere."""
 import ctypes
 import os
 import random
@@ -97,10 +99,26 @@ KNOBS = ((("breakpoints_batch", 1),), (("breakpoints_batch", 2),), (("grid", 1),
          (("breakpoints_chunk", 64),), (("breakpoints_runs", 1),))
 
 
+WIDE_KNOBS = ((("breakpoints_batch", 1),), (("breakpoints_chunk", 7),))  # (beside the first call of every case, which sets no knob)
+
+
 @pytest.mark.parametrize("k", BC.KS)
 def test_cases(k):
+    assert run_cases(k, BC.cases(), KNOBS) > 0
+
+
+@pytest.mark.parametrize("k", BC.WIDE_KS)
+def test_wide_cases(k):
+    """the same structures at keys of two, three and four words with a full and a 2-bit top word, without a knob and under
+    two: a text seam every 7 bytes falls inside k-mers of up to 127 bases"""
+    assert run_cases(k, BC.wide_cases(), WIDE_KNOBS) == 0
+
+
+def run_cases(k, cases, knobs):
+    """every case of `cases` at k, without a knob and under every knob, against the restatement -> the reruns seen under the
+    "breakpoints_runs" knob"""
     reruns_seen = 0
-    for case in (c for c in BC.cases() if c["k"] == k):
+    for case in (c for c in cases if c["k"] == k):
         p = case["params"]
         ref, names = case["ref"], case["names"]
         recs, text, stats, _, with_ref = BC.run(case)
@@ -113,7 +131,7 @@ def test_cases(k):
         # the knobs, on the handle that holds the reference now
         want = want_of(*B.call(with_ref, k, case["ncols"], ref, names, p["min_ref"], p["max_ref"], p["ref_edges"], ref_loaded=True)[:3])
         assert want[:2] == want_of(recs, text, stats)[:2]
-        for kn in KNOBS:
+        for kn in knobs:
             for key, v in kn:
                 g.configure(key, v)
             got, reruns = device_run(g, k, ref, names, p["min_ref"], p["max_ref"], p["ref_edges"], ref_loaded=True)
@@ -132,7 +150,7 @@ def test_cases(k):
                 g.configure(kn[0][0], 0)
                 assert all(n <= kn[0][1] for n in pieces) and sum(pieces) == len(want[1]) and len(pieces) >= len(want[1]) // kn[0][1]
         g.close()
-    assert reruns_seen > 0
+    return reruns_seen
 
 
 def rc(s):
@@ -172,7 +190,7 @@ def genome_case(k):
     return R.build(cols + [[]], k), [chr1, chr2]
 
 
-@pytest.mark.parametrize("k", BC.KS)
+@pytest.mark.parametrize("k", BC.KS + BC.WIDE_KS)
 def test_random_genome(k):
     graph, ref = genome_case(k)
     names = ["one", "two"]

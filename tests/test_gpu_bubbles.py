@@ -3,7 +3,8 @@ equality: every record field, the text bytes and every stat.  Every case of bubb
 and two words); the same with "bubbles_batch" 1 and 2, "grid" 1 and "bubbles_chunk" 1, 7 and 64, where a seam falls inside
 headers, sequences and the blank line; a random 2 kb genome per k (with a repeat that differs in one base) whose second and third colour carry 10 substitutions
 and 2 indels, with and without a haploid colour and at two table capacities; a graph without a fork; the ABI symbol and the
-refusals."""
+refusals.  At k = 63, 65, 95, 97 and 127 (keys of two, three and four words): the wide cases without a knob, with
+"bubbles_batch" 1 and with "bubbles_chunk" 7, and the random genome."""
 import ctypes
 import os
 import random
@@ -84,17 +85,32 @@ def test_abi_symbol_and_wrapper():
 KNOBS = ((), (("bubbles_batch", 1),), (("bubbles_batch", 2),), (("grid", 1),), (("bubbles_chunk", 1),), (("bubbles_chunk", 7),), (("bubbles_chunk", 64),))
 
 
+WIDE_KNOBS = ((), (("bubbles_batch", 1),), (("bubbles_chunk", 7),))
+
+
 @pytest.mark.parametrize("k", BC.KS)
 def test_cases(k):
+    run_cases(k, BC.cases(), KNOBS)
+
+
+@pytest.mark.parametrize("k", BC.WIDE_KS)
+def test_wide_cases(k):
+    """the same structures at keys of two, three and four words with a full and a 2-bit top word, under three of the knobs:
+    a text seam every 7 bytes falls inside k-mers of up to 127 bases"""
+    run_cases(k, BC.wide_cases(), WIDE_KNOBS)
+
+
+def run_cases(k, cases, knobs):
+    """every case of `cases` at k under every knob against the restatement"""
     handles = {}
-    for case in (c for c in BC.cases() if c["k"] == k):
+    for case in (c for c in cases if c["k"] == k):
         g = handles.get(id(case["graph"]))
         if g is None:
             g = handles[id(case["graph"])] = load(case["graph"], k, case["ncols"])
         recs, text, stats, _ = BC.run(case)
         want = want_of(recs, text, stats)
         p = case["params"]
-        for kn in KNOBS:
+        for kn in knobs:
             for key, v in kn:
                 g.configure(key, v)
             got = device_run(g, k, p["max_allele"], p["max_flank"], p["haploid"], p["keep_serial"])
@@ -131,17 +147,18 @@ def genome_case(k):
     return R.build([[c] for c in cols], k)
 
 
-@pytest.mark.parametrize("k", BC.KS)
+@pytest.mark.parametrize("k", BC.KS + BC.WIDE_KS)
 def test_random_genome(k):
     graph = genome_case(k)
-    wants = {hap: want_of(*B.call(graph, k, 3, 100, 60, hap)[:3]) for hap in ((), (0,))}
+    max_allele = BC.limit(100, k)  # (100 at every k of KS; at k = 127 no allele is as short as 100 k-mers)
+    wants = {hap: want_of(*B.call(graph, k, 3, max_allele, 60, hap)[:3]) for hap in ((), (0,))}
     assert wants[()][2]["bubbles"] > 0 and wants[(0,)][2]["haploid_dropped"] > 0 and wants[()][2]["haploid_dropped"] == 0
     for cap in (1 << 13, 1 << 16):
         g = load(graph, k, 3, cap)
         for hap in ((), (0,)):
             for batch in (0, 5):
                 g.configure("bubbles_batch", batch)
-                got = device_run(g, k, 100, 60, hap)
+                got = device_run(g, k, max_allele, 60, hap)
                 print("k=%d cap=%d hap=%s batch=%d: %s" % (k, cap, hap, batch, got[2]))
                 check(got, wants[hap], (k, cap, hap, batch))
         g.close()

@@ -3,7 +3,9 @@ contigs_restate.py, by exact equality: every record field (the doubles bit for b
 Every case of contigs_cases.py (k = 5, 9, 31, 33: keys of one and two words); the same with "contigs_batch" 1 and 2,
 "contigs_nodes" 2, "contigs_held" 1 and "grid" 1, where the output is identical and the rerun counter moves; the load
 round trip of links made by Graph.thread; a k-mer that is not in the graph; a random 2 kb genome with a repeat per k,
-threaded on the device, every key a seed, both seeding modes; the refusals."""
+threaded on the device, every key a seed, both seeding modes; the refusals.  At k = 63, 65, 95, 97 and 127 (keys of two,
+three and four words): the wide cases under three of the knobs, the random genome, and at k = 63, 95, 127 the file of keys
+that agree in their high words, loaded, written back and walked from every key and from shuffled seed reads."""
 import os
 import random
 import sys
@@ -15,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import clean_restate as R  # noqa: E402
 import contigs_cases as CC  # noqa: E402
 import contigs_restate as G  # noqa: E402
+import links_cases as LC  # noqa: E402
 import thread_restate as T  # noqa: E402
 import mccortex_amd as mcx  # noqa: E402
 
@@ -79,11 +82,29 @@ def check(got, want, what):
 KNOBS = ((), (("contigs_batch", 1),), (("contigs_batch", 2),), (("contigs_nodes", 2),), (("contigs_held", 1),), (("grid", 1),))
 
 
+WIDE_KNOBS = ((), (("contigs_batch", 1),), (("contigs_nodes", 2),))
+
+
 @pytest.mark.parametrize("k", CC.KS)
 def test_cases(k):
+    reruns = run_cases(k, CC.cases(), KNOBS)
+    assert reruns[()] == 0 and reruns[(("contigs_batch", 1),)] == 0 and reruns[(("grid", 1),)] == 0
+    assert reruns[(("contigs_nodes", 2),)] > 0 and reruns[(("contigs_held", 1),)] > 0, reruns
+
+
+@pytest.mark.parametrize("k", CC.WIDE_KS)
+def test_wide_cases(k):
+    """the same structures at keys of two, three and four words with a full and a 2-bit top word, under three of the knobs"""
+    reruns = run_cases(k, CC.wide_cases(), WIDE_KNOBS)
+    assert reruns[()] == 0 and reruns[(("contigs_batch", 1),)] == 0
+    assert reruns[(("contigs_nodes", 2),)] > 0, reruns
+
+
+def run_cases(k, cases, knobs):
+    """every case of `cases` at k under every knob against the restatement -> the reruns per knob"""
     handles = {}
-    reruns = {kn: 0 for kn in KNOBS}
-    for case in (c for c in CC.cases() if c["k"] == k):
+    reruns = {kn: 0 for kn in knobs}
+    for case in (c for c in cases if c["k"] == k):
         g = handles.get(id(case["graph"]))
         if g is None:
             g = handles[id(case["graph"])] = load(case["graph"], k, case["ncols"])
@@ -92,7 +113,7 @@ def test_cases(k):
         if text:
             assert g.links_load_text(text) == (len(case["links"]), 0)
         want = want_of(*CC.run(case), k)
-        for kn in KNOBS:
+        for kn in knobs:
             for key, v in kn:
                 g.configure(key, v)
             recs, seq, st = device_run(g, case)
@@ -105,8 +126,7 @@ def test_cases(k):
             reruns[kn] += int(st.reruns)
     for g in handles.values():
         g.close()
-    assert reruns[()] == 0 and reruns[(("contigs_batch", 1),)] == 0 and reruns[(("grid", 1),)] == 0
-    assert reruns[(("contigs_nodes", 2),)] > 0 and reruns[(("contigs_held", 1),)] > 0, reruns
+    return reruns
 
 
 def genome_case(k):
@@ -125,7 +145,7 @@ def genome_case(k):
     return R.build([[gen]], k), reads
 
 
-@pytest.mark.parametrize("k", CC.KS)
+@pytest.mark.parametrize("k", CC.KS + CC.WIDE_KS)
 def test_random_genome_round_trip_and_all_seeds(k):
     graph, reads = genome_case(k)
     g = load(graph, k)
@@ -157,6 +177,40 @@ def test_random_genome_round_trip_and_all_seeds(k):
             check(got_of(recs, seq, st), want, (k, flags, batch))
     g.configure("contigs_batch", 0)
     assert want[2]["wlk_steps"][G.USELINKS] > 0
+    g.close()
+
+
+@pytest.mark.parametrize("k", LC.SHARED_KS)
+def test_keys_that_agree_in_their_high_words(k):
+    """the file of links_cases.shared_high_words on a graph of exactly its k-mers (no edges): groups of keys that differ in
+    their last word only, or first in a middle word with the lower words sorting the other way round, and k-mer lines
+    that hold the reverse complement.  The load (k_cg_kmers), the store's key sort and its text (k_th_text), then contigs
+    with every key a seed (k_cg_keyword and the key sort) and with the k-mers as seed reads in shuffled order"""
+    text, groups = LC.shared_high_words(k)
+    kmers = [s for _, ks, _ in groups for s in ks]
+    graph = R.build([kmers], k)
+    assert sorted(graph) == sorted(R.kmer_int(s) for s in kmers) and not any(ed[0] for _, ed in graph.values())
+    g = load(graph, k)
+    links = LC.stored(text, k)
+    nlines = sum(ln[:2] in (b"F ", b"R ") for ln in text.split(b"\n"))
+    assert g.links_load_text(text) == (nlines, 0)
+    body = CC.links_text({"k": k, "links": links})
+    info = {"num_kmers_with_paths": len({l[0] for l in links}), "num_paths": len(links), "path_bytes": sum((len(l[2]) + 3) // 4 for l in links)}
+    assert g.links_text(seq=False) == body and g.links_info() == info
+    g.links_reset()
+    assert g.links_load_text(body) == (len(links), 0)
+    assert g.links_text(seq=False) == body and g.links_info() == info
+    conf = G.conf_table({}, len(graph))
+    rng = random.Random(k)
+    seeds = [s if rng.random() < 0.5 else LC.revcomp(s) for s in kmers] + kmers[:2]
+    rng.shuffle(seeds)
+    for sd in (None, seeds):
+        for flags in (0, G.RESEED):
+            want = want_of(*G.assemble(graph, k, links, conf, 0, flags, 0, -1.0, -1.0, sd), k)
+            recs, seq, st = g.contigs(conf, seeds=sd, reseed=bool(flags & G.RESEED))
+            check(got_of(recs, seq, st), want, (k, sd is None, flags))
+            keys = [r[0] for r in want[0]]
+            assert len(keys) == len(kmers) + (2 if sd and flags else 0) and (keys == sorted(keys)) == (sd is None)
     g.close()
 
 

@@ -1,6 +1,6 @@
 """`correct` on the MI355X (Graph.correct, csrc/mcx_correct.h) against the CPU restatement in correct_restate.py: the
 bytes, out_off and every count of mcx_correct_stats, by exact equality.  The golden graphs (k = 9 and k = 11) and the
-random case of correct_cases.py (k = 11, 31, 33, 63, 95: keys of one to three words; one colour, and three with the
+random case of correct_cases.py (k = 11, 31, 33, 63, 65, 95, 97, 127: keys of one to four words; one colour, and three with the
 sample in colour 1), with and without qualities, one-way and two-way, in tables of two sizes, with "grid" = 1 and with
 "reads_chunk" = 256, which cuts the 600-base reads into pieces with an error over a seam.  The case first asserts on
 the restatement alone that it reaches every rule at least three times (test_correct_restate.py asserts the same on the

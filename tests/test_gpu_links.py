@@ -1,6 +1,7 @@
 """`links` on the MI355X (mccortex_amd.Links, csrc/mcx_links.h; the `links` command) against the CPU restatement in
 links_restate.py: the .ctp body and the list text byte for byte, the statistics and the histogram by exact equality.
-Generated files of links_cases.py (k = 5, 31, 33) under every option; links around the 32-junction word seams; one hot
+Generated files of links_cases.py (k = 5, 31, 33, 63, 65, 95, 97, 127) and its files of k-mers that agree in their high
+key words (k = 63, 95, 127) under every option; links around the 32-junction word seams; one hot
 k-mer as a comb and as a bush of 4096 links (their expected texts are kept as digests in golden/links.json, written from
 the restatement, which takes its time over 8 million tree steps); the file in pieces, with "grid" = 1 and an
 "out_chunk" of 64 bytes; every refusal; the device's own links; the command."""
@@ -71,7 +72,7 @@ def check(k, text, what, pieces=None, knobs=(), max_kmers=0, **opt):
     return got
 
 
-FILES = {k: LC.generated(k, n, seed=k) for k, n in ((5, 300), (31, 200), (33, 200))}
+FILES = {k: LC.generated(k, n, seed=k) for k, n in ((5, 300), (31, 200), (33, 200), (63, 200), (65, 200), (95, 200), (97, 200), (127, 200))}
 
 
 @pytest.mark.parametrize("name", sorted(OPTIONS))
@@ -83,6 +84,19 @@ def test_generated(k, name):
         assert got[0] == b"" and got[2]["links"] == 0 and got[2]["kmers_with_links"] == 0 and got[1].count(b"\n") < got[2]["tree_links"] // 10
     if name == "plain":
         assert got[2]["links"] > 0 and b"\nR " in got[0] and got[2]["links"] < got[2]["links_in"]
+
+
+@pytest.mark.parametrize("name", sorted(OPTIONS))
+@pytest.mark.parametrize("k", LC.SHARED_KS)
+def test_keys_that_agree_in_their_high_words(k, name):
+    """k-mers in groups that differ in their last bases only, or first in a middle key word, some written as the reverse
+    complement: the blocks come out per k-mer line as written, in the order of the file"""
+    text, groups = LC.shared_high_words(k)
+    got = check(k, text, "shared k=%d %s" % (k, name), **OPTIONS[name])
+    if name == "plain":
+        heads = [ln.split(b" ")[0] for ln in text.split(b"\n") if ln[:1] in (b"A", b"C", b"G", b"T")]
+        assert [ln.split(b" ")[0] for ln in got[0].split(b"\n") if ln[:1] in (b"A", b"C", b"G", b"T")] == heads
+        assert got[2]["kmers_read"] == len(heads) == sum(len(kmers) for _, kmers, _ in groups)
 
 
 def test_word_seams():

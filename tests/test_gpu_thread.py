@@ -1,7 +1,7 @@
 """`thread` on the MI355X (Graph.thread, Graph.links_*, csrc/mcx_thread.h) against the CPU restatement in
 thread_restate.py: the text, the totals, the contig histogram and every count of mcx_thread_stats, by exact equality.
-The golden graph of the reference's unit test (k = 11) and the random case of thread_cases.py (k = 11, 31, 33, 63, 95:
-keys of one to three words), one-way and two-way, in tables of two sizes, with "grid" = 1 and with "reads_chunk" = 256,
+The golden graph of the reference's unit test (k = 11) and the random case of thread_cases.py (k = 11, 31, 33, 63, 65, 95,
+97, 127: keys of one to four words), one-way and two-way, in tables of two sizes, with "grid" = 1 and with "reads_chunk" = 256,
 which cuts the 600-base reads into pieces with an error over a seam; the reads in one call and in three, the reads
 aimed at a structure in one call, in three and one read per call; links_reset; a count that stays at 255; links cut to
 three junctions; the refusals."""

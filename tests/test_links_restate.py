@@ -141,6 +141,47 @@ def test_golden_is_current():
     assert os.path.getsize(os.path.join(HERE, "golden", "links.json")) < 16384
 
 
+@pytest.mark.parametrize("k", LC.SHARED_KS)
+def test_shared_high_words(k):
+    """the file of k-mers that agree in their high key words is what it says: every k-mer is canonical as the groups hold
+    it, a group that differs in the last word agrees in every other, a group of word j agrees above it, differs in it and
+    sorts the other way round below it; the file holds the last group's k-mers turned round, and the usual noise"""
+    text, groups = LC.shared_high_words(k)
+    W = (2 * k + 63) // 64
+    assert text == LC.shared_high_words(k)[0] and W == {63: 2, 95: 3, 127: 4}[k]
+    assert sorted(j for j, _, _ in groups) == list(range(1, W - 1)) + [W - 1] * 4
+    lines = text.decode().split("\n")
+    heads = [ln.split(" ")[0] for ln in lines if ln[:1] in ("A", "C", "G", "T")]
+    assert len(heads) == len(set(heads)) == sum(len(kmers) for _, kmers, _ in groups)
+    assert heads != sorted(heads) and any(ln == "" for ln in lines[:-1]) and any(ln.startswith("#") for ln in lines)
+    for j, kmers, turned in groups:
+        assert len(kmers) >= 4 and len(set(kmers)) == len(kmers)
+        words = [LC.key_words(s) for s in kmers]
+        for s in kmers:
+            assert len(s) == k and R.canon(R.kmer_int(s), k) == R.kmer_int(s)
+            assert (LC.revcomp(s) if turned else s) in heads and (s if turned else LC.revcomp(s)) not in heads
+        assert len({tuple(w[:j]) for w in words}) == 1 and len({w[j] for w in words}) == len(kmers)
+        if j == W - 1:
+            assert len({s[:32 * (W - 1)] for s in kmers}) == 1
+        else:
+            by_j = sorted(words, key=lambda w: w[j])
+            assert by_j == sorted(words) and by_j == sorted(words, key=lambda w: w[j + 1:], reverse=True)
+    assert sum(turned for _, _, turned in groups) == 1
+    # the words are those of the packed records
+    s = groups[0][1][0]
+    assert R.pack({R.kmer_int(s): ((1,), [0])}, k, 1)[:8 * W] == b"".join(w.to_bytes(8, "little") for w in LC.key_words(s))
+    # what a graph keeps of it: the turned k-mers under their canonical keys, their links the other way round
+    links = LC.stored(text, k)
+    assert {key for key, _, _, _ in links} == {R.kmer_int(s) for _, kmers, _ in groups for s in kmers}
+    turned = next(kmers for _, kmers, t in groups if t)
+    blk = next(b.decode() for b in LC.blocks_of(text) if LC.revcomp(turned[0]) + " " in b.decode())
+    ln = next(x for x in blk.split("\n") if x[:2] in ("F ", "R "))
+    assert (R.kmer_int(turned[0]), "RF".index(ln[0]), tuple("ACGT".index(c) for c in ln.split(" ")[3])) in {l[:3] for l in links}
+    assert all(1 <= n <= 255 for _, _, _, n in links) and any(n == 255 for _, _, _, n in links)
+    ctp, lst, st, _ = LR.links(text, k)
+    assert st["kmers_read"] == len(heads) and st["links_in"] > st["num_links"] > 0
+
+
 def test_generators_cover_the_ground():
     text = LC.generated(31, 200, seed=31)
     lines = text.decode().split("\n")

@@ -24,7 +24,7 @@ import correct_restate as C  # noqa: E402
 import reads_restate as S  # noqa: E402
 import thread_restate as T  # noqa: E402
 
-KS = (11, 31, 33, 63, 95)
+KS = (11, 31, 33, 63, 65, 95, 97, 127)
 REACH = ("junction_in_filled_gap", "ended_by_missing_edge", "ended_by_failed_gap", "step_back", "reverse_link", "same_link_twice_by_one_read",
          "one_kind_only")
 COMB_SHARED = 48
